@@ -1,6 +1,9 @@
 """bench.py — denoiser DDPM-step throughput on synthetic Breaking-Bad-shaped puzzles.
 
-    python bench.py --gpus N --steps K --warmup W [--mode train|sample]
+    python bench.py --gpus N --steps K --warmup W [--mode train|sample] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line; --full adds everything else listed below.
+--dump-outputs DIR writes what the timed path computed in its last timed step as DIR/<name>.npy (float32, seeded inputs).
 
 Default (--mode train) = BASELINE.json configs[1]: one "step" is one DDPM TRAINING iteration of the denoiser
 over a batch resident in HBM (Denoiser.training_step, puzzlefusion_plusplus/denoiser/model/denoiser.py:80-145):
@@ -9,7 +12,7 @@ noisy pose -> frozen PointNet++/VQ-VAE encode -> DenoiserTransformer forward in 
 MSE over valid non-reference fragments -> full backward -> (N > 1: gradient all-reduce over RCCL, overlapped
 with the backward) -> AdamW.  Nothing is skipped inside the timed region.
 --mode sample: one step = one DDPM sampler step (Denoiser.validation_step loop body, denoiser.py:172-185),
-reported under "extra" in the default mode.
+reported under "extra" of a --full training run.
 Workload shape on every GPU: 32 puzzles x 20 fragment slots x 1024 points, valid-fragment counts from
 SURVEY.md §8d's distribution.  N > 1: one process per GPU, different puzzles per rank (weak scaling).
 
@@ -18,7 +21,7 @@ SURVEY.md §8d's distribution.  N > 1: one process per GPU, different puzzles pe
 operands travel as split planes; the line carries max |pred_noise(single pass) - pred_noise(f16x3)| next to the throughput.
 Beyond the reference's max_len = 20: no reference parity exists for this shape, roofline only.
 
-Prints ONE JSON line (rank 0) with the extra objects:
+Prints ONE JSON line (rank 0); with --full it carries the extra objects:
   roofline     — dominant GEMM kernel of the step: algorithmic FLOPs of its launches / their HIP-event durations against the
                  matrix-core ceiling of its arithmetic (f16 dense peak / 3 for the split-f16 kernels)
   roofline_hbm — the bandwidth / latency regime (reported separately): FPS, ball query, rotate, VQ, LayerNorm,
@@ -99,9 +102,41 @@ def parse():
                     help="train mode: run the frozen encoder of each iteration in line instead of one iteration ahead on its own stream")
     ap.add_argument("--compact", action="store_true",
                     help="drop padded fragment slots in the transformer (valid-fragment outputs unchanged)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: leave out the roofline passes and the other modes' figures")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also measure the rooflines, the HBM-regime kernels, the other modes at the same "
+                         "shape, the stress and auto-agglomerative figures, the stand-alone all-reduce and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_PARAM_SAMPLE = 1 << 22        # --dump-outputs, training: a fixed, seeded sample of the updated parameters (16 MB in float32)
+
+
+def dump_outputs(wl, out_dir: str) -> dict:
+    """--dump-outputs: the arrays a caller of the timed step receives after its last timed step, as float32 .npy files.
+    Training: the loss and a seeded sample of the updated denoiser parameters (all 57.6 M would be 230 MB); sampler: the stepped
+    poses and the predicted noise; stress: those and the verifier's edge logits.  -> {name: shape}"""
+    import numpy as np
+
+    if isinstance(wl, TrainWorkload):
+        flat = torch.cat([p.detach().reshape(-1) for _, p in wl.model.denoiser.named_parameters()])
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, flat.numel(), (min(DUMP_PARAM_SAMPLE, flat.numel()),), generator=g).sort().values
+        arrays = {"loss": wl.last_loss, "denoiser_params_sample": flat[idx.to(flat.device)]}
+    else:
+        arrays = {"x_prev": wl.x, "pred_noise": wl.last_eps}
+        if isinstance(wl, StressWorkload):
+            arrays["verifier_logits"] = wl.last_logits
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 class SamplerWorkload:
@@ -133,6 +168,7 @@ class SamplerWorkload:
             v_._pfpp_t = int(t_)          # as Denoiser.sample / AutoAgglomerative tag them: AdaLN rows cached per (t, batch)
         self.x = self.x0.clone()
         self.i = 0
+        self.last_eps = None
 
     @torch.no_grad()
     def step(self):
@@ -145,6 +181,7 @@ class SamplerWorkload:
         eps = m.denoiser(self.x, self.ts_dev[t], latent, xyz, d["part_valids"], d["part_scale"], self.ref)
         self.x = m.noise_scheduler.step(eps, t, self.x, variance_noise=self.noise[k], ref_part=self.ref,
                                         reference=self.reference).prev_sample
+        self.last_eps = eps
         self.i += 1
 
 
@@ -762,10 +799,14 @@ def main():
         ff = torch.tensor([frag_steps], dtype=torch.float64, device=dev)
         dist.all_reduce(ff, op=dist.ReduceOp.SUM)
         frag_steps = ff.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
 
+    # everything below the headline figure is measured with --full only; a plain run prints its line next
+    with_roofline = args.full and not args.no_roofline
     # ---- roofline of the dominant kernel: second, instrumented pass over the same steps ----------
     roofline = None
-    if not args.no_roofline:
+    if with_roofline:
         if train:
             # per-kernel durations are taken with the streams serialised (no side stream, encoder in line): bracketing
             # events on a stream that shares the chip with another stream measure the contention too, not the kernel
@@ -792,7 +833,7 @@ def main():
         extra["backend"] = backend
     if balance is not None:
         extra["rank_balance"] = balance
-    if dist is not None and train and world > 1:
+    if args.full and dist is not None and train and world > 1:
         # the step's one exchange, alone: all-reduce of the flat gradient buffer (what GradExchange sends in 6 layer slices + 2)
         gbuf = wl.engine.flat.grads
         for _ in range(2):
@@ -809,12 +850,14 @@ def main():
                                         "busbw_GBps": round(nbytes / t_ar * 1e-9 * 2 * (world - 1) / world, 1),
                                         "note": "stand-alone, not overlapped; in the step it runs per layer under the backward"}
     roofline_hbm = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and with_roofline:
         if stress:
             roofline_hbm = hbm_regime(dev, wl.n_frag, 2048, wl.n_frag * 25)
         else:
             roofline_hbm = hbm_regime(dev, wl.n_frag, args.points, wl.n_frag * 25 if (train or args.compact) else args.batch * 20 * 25)
     if stress and rank == 0:
+        extra["verifier_edges_per_puzzle"] = int(wl.edge_feat.shape[1])
+    if args.full and stress and rank == 0:
         # accuracy of the perf mode: the same first sampler step in the parity arithmetic (split-f16, 3 matrix instructions per product)
         eps_fast = wl.pred_noise_at_start()
         ops.SINGLE_PASS = False
@@ -825,10 +868,9 @@ def main():
                                          "max_abs_pred_noise": float(eps_ref[v].abs().max()),
                                          "note": "first sampler step, same inputs and weights; f16x3 is the parity mode (1e-4 vs the CPU oracle), "
                                                  "single-pass fp16 the perf mode of BASELINE configs[4]"}
-        extra["verifier_edges_per_puzzle"] = int(wl.edge_feat.shape[1])
     if train and rank == 0:
         extra["final_loss"] = round(float(wl.last_loss), 5)
-    if train and rank == 0 and world == 1 and not args.no_roofline and not args.latents_given:
+    if train and rank == 0 and world == 1 and with_roofline and not args.latents_given:
         # BASELINE configs[1] reads "VQ-VAE latents precomputed": the same iteration without the encoder (latents of the clean
         # pose, computed once) — not a mode of the reference (its latents depend on the noisy rotation, denoiser.py:66-71)
         del wl.engine
@@ -845,7 +887,7 @@ def main():
                                         "ms_per_step": round(dt / args.steps * 1e3, 3),
                                         "note": "transformer-only training iteration (forward, loss, backward, AdamW), encoder skipped"}
         del lwl.engine, lwl
-    if train and rank == 0 and world == 1 and not args.no_roofline:
+    if train and rank == 0 and world == 1 and with_roofline:
         # the inference sampler step at the same shape (Denoiser.validation_step loop body), padded slots
         # evaluated like the reference and dropped
         if hasattr(wl, "engine"):
@@ -913,7 +955,7 @@ def main():
             ops.GEMM_TRACE = None
         extra["auto_aggl_full_loop"] = aggl_puzzles_per_s(dev)
         extra["auto_aggl_full_loop_batched"] = aggl_puzzles_per_s(dev, n_puzzles=64, in_flight=32)
-    if not train and not stress and rank == 0 and world == 1 and not args.compact and not args.no_roofline:
+    if not train and not stress and rank == 0 and world == 1 and not args.compact and with_roofline:
         # the same K steps with the padded fragment slots dropped (outputs of valid fragments unchanged)
         wl.model.denoiser.compact_padded = True
         for _ in range(args.warmup):
@@ -929,7 +971,7 @@ def main():
                                  "ms_per_step": round(dt / args.steps * 1e3, 3),
                                  "note": "padded fragment slots dropped in the transformer; identical predictions for valid fragments"}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if train:
             # the line's own workload (training iterations) on the CPU port, and next to it BASELINE.md section 3's protocol as written
             # (the 20-step eval sampler on configs[0]) — the figure the plan names; both bounded, both on this host in this run
