@@ -1060,6 +1060,49 @@ int pfpp_heads_bwd(const float* dout, const int32_t* slot, const pfpp_head_param
                    const pfpp_head_grads* g_trans, const pfpp_head_grads* g_rot, float grad_scale, float* dx, int64_t L,
                    pfpp_stream_t stream);
 
+/* ==== verifier training (csrc/verifier_train.hip) ====================================================================
+ * Verifier.training_step / _loss / configure_optimizers (verifier/model/verifier.py:20-69, 100-107) around
+ * VerifierTransformer.forward (verifier_transformer.py:45-58) in train mode: nn.TransformerEncoderLayer(d_model 256, nhead 8,
+ * dim_feedforward 2048, dropout 0.1, activation gelu, batch_first, post-norm).  The projections, LayerNorm + dropout sites,
+ * gradient GEMMs and AdamW are the denoiser's kernels above; these are the verifier-only pieces.  Dropout masks use the
+ * generator of pfpp_dropout (keep = rng(seed, site, counter) >= p * 2^32) and are regenerated in the backward.
+ *
+ * Self-attention with dropout on the probabilities (nn.MultiheadAttention(dropout=0.1) with key_padding_mask = ~edge_valids,
+ * verifier_transformer.py:55 -> torch.nn.functional.multi_head_attention_forward): qkv [B*E, 3*H*dh] = (q | k | v) of the
+ * in-projection, out [B*E, H*dh] = dropout(softmax(q k^T * scale + mask)) v, lse [B*E, H] = log sum_j exp(s_ij) over the valid
+ * keys.  keep(b, h, q, k) = rng(seed, site, ((b*H + h)*E + q)*E + k).  Masked keys have P = 0 exactly.  A sequence without a
+ * valid key produces out = 0, lse = +inf and zero gradients (torch produces NaN there).  One workgroup per (sequence, head),
+ * exact fp32; dh = 32 and E <= 256 only (PFPP_EUNSUPPORTED otherwise).
+ * pfpp_verifier_attn_bwd: dqkv [B*E, 3*H*dh] = (dq | dk | dv) in one launch, using D_i = dO_i . O_i (holds with dropout on P).
+ * pfpp_verifier_attn_dropout_mask: the keep mask as uint8 [B, H, E, E] (tests).                                          */
+int pfpp_verifier_attn_fwd(const float* qkv, float* out, float* lse, const uint8_t* key_valid, int64_t B, int64_t E, int64_t H,
+                           int64_t dh, float scale, float p, uint64_t seed, uint32_t site, pfpp_stream_t stream);
+int pfpp_verifier_attn_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                           const uint8_t* key_valid, int64_t B, int64_t E, int64_t H, int64_t dh, float scale, float p, uint64_t seed,
+                           uint32_t site, pfpp_stream_t stream);
+int pfpp_verifier_attn_dropout_mask(uint8_t* keep, int64_t B, int64_t H, int64_t E, float p, uint64_t seed, uint32_t site,
+                                    pfpp_stream_t stream);
+
+/* mlp_out + weighted BCE (verifier_transformer.py:57, verifier.py:20-47), one pass over h6 [M, C] (C = 256):
+ *   logits[r] = h6[r] . w + b[0]  (every row);  over the N valid rows (valid[r] != 0), weight w_r = neg_weight if target == 0 else 1:
+ *   loss = sum_r w_r (max(x,0) - x y + log1p(exp(-|x|))) / N   (mean over N, not over sum w; 0 when N = 0)
+ *   dlogit[r] = w_r (sigmoid(x) - y) / N (0 for invalid rows), dh6 = dlogit (x) w (optional), dw += sum_r dlogit h6, db += sum_r dlogit
+ *   stats int32[4] = (tp, fp, tn, fn) of pred = fp32 sigmoid(x) > 0.5 against target > 0.5;  amax (optional) = max |dlogit|.
+ * Other modes: dlogit_in != NULL (the head's backward for an upstream gradient of the logits): d = dlogit_in[r] on every row, no
+ * loss / counts (written as 0); target == NULL and dlogit_in == NULL: logits only.
+ * Gradients are unscaled fp32 (the gradient GEMMs lift their operands, pfpp_gemm_grad a_scale).  workspace: fp64
+ * [pfpp_verifier_head_bce_workspace()] zeroed once by the caller; every call leaves it zeroed again (not shared by concurrent calls). */
+int pfpp_verifier_head_bce(const float* h6, const float* w, const float* b, const float* target, const uint8_t* valid,
+                           const float* dlogit_in, int64_t M, int64_t C, float neg_weight, float* logits, float* dlogit, float* dh6, float* dw, float* db, float* loss,
+                           int32_t* stats, float* amax, double* workspace, pfpp_stream_t stream);
+int64_t pfpp_verifier_head_bce_workspace(void);
+
+/* GELU (exact erf) + dropout of the feed-forward (TransformerEncoderLayer._ff_block: dropout(gelu(linear1(x)))), flat n (% 4 == 0):
+ *   fwd: u = gelu(z) keep / (1-p);   bwd: dz = gelu'(z) keep / (1-p) du;   keep = rng(seed, site, i)                              */
+int pfpp_verifier_gelu_dropout(const float* z, float* u, int64_t n, float p, uint64_t seed, uint32_t site, pfpp_stream_t stream);
+int pfpp_verifier_gelu_dropout_bwd(const float* z, const float* du, float* dz, int64_t n, float p, uint64_t seed, uint32_t site,
+                                   pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -310,6 +310,13 @@ SIGNATURES = {
     "pfpp_attn_dense_train_p": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _f32, _pl, _p],
     "pfpp_attn_dense_bwd_p": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _f32, _pl, _p],
     "pfpp_attn_blockdiag_bwd_p": [_p, _p, _p, _i64, _i64, _i64, _i64, _f32, _pl, _p],
+    # ---- verifier training (csrc/verifier_train.hip)
+    "pfpp_verifier_attn_fwd": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _u32, _p],
+    "pfpp_verifier_attn_bwd": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _u32, _p],
+    "pfpp_verifier_attn_dropout_mask": [_p, _i64, _i64, _i64, _f32, _u64, _u32, _p],
+    "pfpp_verifier_head_bce": [_p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "pfpp_verifier_gelu_dropout": [_p, _p, _i64, _f32, _u64, _u32, _p],
+    "pfpp_verifier_gelu_dropout_bwd": [_p, _p, _p, _i64, _f32, _u64, _u32, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
@@ -327,6 +334,7 @@ PLAIN = {
     "pfpp_tlayers_bwd_bytes": ([_i64, _i64, _i64, _i64], C.c_int64),
     "pfpp_bn_stats_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_fragment_prepare_workspace": ([_i64, _i64], C.c_int64),
+    "pfpp_verifier_head_bce_workspace": ([], C.c_int64),
 }
 
 # struct name in include/pfpp.h (without the pfpp_ prefix) -> its mirror here; load() compares the sizes

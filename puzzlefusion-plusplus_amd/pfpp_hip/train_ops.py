@@ -781,3 +781,104 @@ def heads_bwd(dout: torch.Tensor, trans, rot, saved, g_trans, g_rot, g_scale: fl
                                      _ptr(da1), _ptr(dp), C.byref(g_trans), C.byref(g_rot), g_scale, _ptr(dx), L, _stream()),
           "pfpp_heads_bwd")
     return da0, da1, (dx if want_dx else dp)
+
+
+# ---- verifier training (csrc/verifier_train.hip) --------------------------------------------------------------------------------
+def verifier_attn_fwd(qkv: torch.Tensor, key_valid: torch.Tensor, B: int, E: int, H: int, dh: int, scale: float, p: float,
+                      seed: int, site: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(out [B*E, H*dh], lse [B*E, H]) of the key-masked self-attention with dropout on the probabilities (pfpp_verifier_attn_fwd);
+    qkv [B*E, 3*H*dh], key_valid uint8 [B, E]"""
+    _chk(qkv, _f32, "qkv"); _chk(key_valid, torch.uint8, "key_valid")
+    if qkv.shape != (B * E, 3 * H * dh) or key_valid.numel() != B * E:
+        raise ValueError("verifier_attn_fwd: qkv must be [B*E, 3*H*dh] and key_valid [B, E]")
+    if out is None:
+        out = torch.empty((B * E, H * dh), dtype=_f32, device=qkv.device)
+    lse = torch.empty((B * E, H), dtype=_f32, device=qkv.device)
+    check(_lib.load().pfpp_verifier_attn_fwd(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(key_valid), B, E, H, dh, scale, p, seed, site,
+                                             _stream()), "pfpp_verifier_attn_fwd")
+    return out, lse
+
+
+def verifier_attn_bwd(qkv: torch.Tensor, out_fwd: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, key_valid: torch.Tensor,
+                      B: int, E: int, H: int, dh: int, scale: float, p: float, seed: int, site: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dqkv [B*E, 3*H*dh] = (dq | dk | dv) in one launch (pfpp_verifier_attn_bwd)"""
+    _chk(qkv, _f32, "qkv"); _chk(out_fwd, _f32, "out_fwd"); _chk(dout, _f32, "dout"); _chk(lse, _f32, "lse")
+    _chk(key_valid, torch.uint8, "key_valid")
+    if qkv.shape != (B * E, 3 * H * dh) or dout.shape != (B * E, H * dh) or out_fwd.shape != dout.shape or lse.shape != (B * E, H):
+        raise ValueError("verifier_attn_bwd: shape mismatch")
+    if out is None:
+        out = torch.empty_like(qkv)
+    check(_lib.load().pfpp_verifier_attn_bwd(_ptr(qkv), _ptr(out_fwd), _ptr(dout), _ptr(lse), _ptr(out), _ptr(key_valid), B, E, H, dh,
+                                             scale, p, seed, site, _stream()), "pfpp_verifier_attn_bwd")
+    return out
+
+
+def verifier_attn_dropout_mask(B: int, H: int, E: int, p: float, seed: int, site: int, device) -> torch.Tensor:
+    """the keep mask of the attention probabilities as uint8 [B, H, E, E] (tests)"""
+    keep = torch.empty((B, H, E, E), dtype=torch.uint8, device=device)
+    check(_lib.load().pfpp_verifier_attn_dropout_mask(_ptr(keep), B, H, E, p, seed, site, _stream()), "pfpp_verifier_attn_dropout_mask")
+    return keep
+
+
+def verifier_head_workspace(device) -> torch.Tensor:
+    """the zeroed fp64 workspace of verifier_head_bce (every call leaves it zeroed again)"""
+    return torch.zeros(int(_lib.load().pfpp_verifier_head_bce_workspace()), dtype=torch.float64, device=device)
+
+
+def verifier_head_bce(h6: torch.Tensor, w: torch.Tensor, b: torch.Tensor, target: Optional[torch.Tensor], valid: Optional[torch.Tensor],
+                      dw: torch.Tensor, db: torch.Tensor, workspace: torch.Tensor, *, neg_weight: float = 0.2, need_dh: bool = True,
+                      amax: Optional[torch.Tensor] = None, dlogit_in: Optional[torch.Tensor] = None):
+    """mlp_out + weighted BCE (pfpp_verifier_head_bce): -> (logits [M], loss [1], dlogit [M], dh6 [M, C] or None, stats int32 [4] =
+    (tp, fp, tn, fn)); dw [C] / db [1] accumulate the head's gradients.  dlogit_in: the head's backward for that upstream gradient
+    instead of the loss; target None (and no dlogit_in): logits only"""
+    for t_, nm in ((h6, "h6"), (w, "w"), (b, "b"), (dw, "dw"), (db, "db")):
+        _chk(t_, _f32, nm)
+    _chk(workspace, torch.float64, "workspace")
+    M, Cc = h6.shape
+    if target is not None:
+        _chk(target, _f32, "target"); _chk(valid, torch.uint8, "valid")
+        if target.numel() != M or valid.numel() != M:
+            raise ValueError("verifier_head_bce: target / valid must have one entry per row")
+    if dlogit_in is not None:
+        _chk(dlogit_in, _f32, "dlogit_in")
+        if dlogit_in.numel() != M:
+            raise ValueError("verifier_head_bce: dlogit_in must have one entry per row")
+    if w.numel() != Cc or dw.numel() != Cc or b.numel() != 1 or db.numel() != 1:
+        raise ValueError("verifier_head_bce: shape mismatch")
+    if workspace.numel() < int(_lib.load().pfpp_verifier_head_bce_workspace()):
+        raise ValueError("verifier_head_bce: workspace too small")
+    dev = h6.device
+    logits = torch.empty((M,), dtype=_f32, device=dev)
+    dlogit = torch.empty((M,), dtype=_f32, device=dev)
+    dh6 = torch.empty_like(h6) if need_dh else None
+    loss = torch.empty((1,), dtype=_f32, device=dev)
+    stats = torch.empty((4,), dtype=torch.int32, device=dev)
+    if amax is not None:
+        _chk(amax, _f32, "amax")
+    check(_lib.load().pfpp_verifier_head_bce(_ptr(h6), _ptr(w), _ptr(b), _ptr(target), _ptr(valid), _ptr(dlogit_in), M, Cc, neg_weight, _ptr(logits),
+                                             _ptr(dlogit), _ptr(dh6), _ptr(dw), _ptr(db), _ptr(loss), _ptr(stats), _ptr(amax),
+                                             _ptr(workspace), _stream()), "pfpp_verifier_head_bce")
+    return logits, loss, dlogit, dh6, stats
+
+
+def verifier_gelu_dropout(z: torch.Tensor, p: float, seed: int, site: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """u = gelu(z) * keep / (1 - p) (pfpp_verifier_gelu_dropout)"""
+    _chk(z, _f32, "z")
+    if out is None:
+        out = torch.empty_like(z)
+    check(_lib.load().pfpp_verifier_gelu_dropout(_ptr(z), _ptr(out), z.numel(), p, seed, site, _stream()), "pfpp_verifier_gelu_dropout")
+    return out
+
+
+def verifier_gelu_dropout_bwd(z: torch.Tensor, du: torch.Tensor, p: float, seed: int, site: int,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dz = gelu'(z) * keep / (1 - p) * du (pfpp_verifier_gelu_dropout_bwd)"""
+    _chk(z, _f32, "z"); _chk(du, _f32, "du")
+    if du.shape != z.shape:
+        raise ValueError("verifier_gelu_dropout_bwd: z and du differ in shape")
+    if out is None:
+        out = torch.empty_like(z)
+    check(_lib.load().pfpp_verifier_gelu_dropout_bwd(_ptr(z), _ptr(du), _ptr(out), z.numel(), p, seed, site, _stream()),
+          "pfpp_verifier_gelu_dropout_bwd")
+    return out
