@@ -1103,6 +1103,48 @@ int pfpp_verifier_gelu_dropout(const float* z, float* u, int64_t n, float p, uin
 int pfpp_verifier_gelu_dropout_bwd(const float* z, const float* du, float* dz, int64_t n, float p, uint64_t seed, uint32_t site,
                                    pfpp_stream_t stream);
 
+/* ---- VQ-VAE pre-training (vqvae/model/fracture_ae.py; csrc/vqvae_train.hip) ----------------------------------------
+ * pfpp_chamfer_fwd: chamferdist.ChamferDistance(r, p, bidirectional=True) (pn2.py:83-97, vq_vae.py:75-89): for every source
+ * point r[b, i] (= off[b, i] + ctr[b, i / rep] when ctr is given: pc_offset + xyz[:, :, None]) the squared distance to, and the
+ * index of, its nearest target point, and the same from every target point to the sources.  The distances equal
+ * pfpp_nn_dist's bit for bit; an exact tie keeps the lowest index.  off [batch, n, 3], ctr [batch, n / rep, 3], tgt
+ * [batch, m, 3]; d_src / i_src [batch, n], d_tgt / i_tgt [batch, m].
+ * pfpp_chamfer_bwd: grad[b, i] = 2 s [(r_i - p_{i_src(i)}) + sum_{j : i_tgt(j) = i} (r_i - p_j)] with s = scale (* gscale[0]
+ * when given, a device scalar) — d loss / d r (= d / d off); written as a gather per source point.
+ * pfpp_chamfer_reduce: loss[0] = scale (sum d_src + sum d_tgt), fp64 accumulation in a fixed order.                     */
+int pfpp_chamfer_fwd(const float* off, const float* ctr, int64_t rep, const float* tgt, float* d_src, int32_t* i_src,
+                     float* d_tgt, int32_t* i_tgt, int64_t batch, int64_t n, int64_t m, pfpp_stream_t stream);
+int pfpp_chamfer_bwd(const float* off, const float* ctr, int64_t rep, const float* tgt, const int32_t* i_src, const int32_t* i_tgt,
+                     float* grad, int64_t batch, int64_t n, int64_t m, float scale, const float* gscale, pfpp_stream_t stream);
+int pfpp_chamfer_reduce(const float* d_src, int64_t n_src, const float* d_tgt, int64_t n_tgt, float scale, float* loss,
+                        pfpp_stream_t stream);
+/* pfpp_vq_train: the training side of VectorQuantizer.forward (quantizer.py:45-67) from z [R, D] and the codes pfpp_vq_encode
+ * wrote (n = R D): out[0] = embedding_loss = (1 + beta) mean((e - z)^2), out[1] = perplexity = exp(-sum_k p_k log(p_k + 1e-10)),
+ * dz = g 2 (z - e) / n (the first term's gradient; the decoder's straight-through gradient is the caller's), dcodebook[k] =
+ * g 2 beta sum_{code = k} (e_k - z) / n (a gather per code), g = g_emb[0] or 1.  dz / dcodebook may be NULL.  D = 16.
+ * workspace: pfpp_vq_train_workspace(R, K) bytes.                                                                         */
+int pfpp_vq_train(const float* z, const float* codebook, const int32_t* codes, int64_t R, int64_t K, int64_t D, float beta,
+                  const float* g_emb, float* dz, float* dcodebook, float* out, void* workspace, pfpp_stream_t stream);
+int64_t pfpp_vq_train_workspace(int64_t R, int64_t K);
+/* pfpp_sa_pool_bwd: backward of max_p relu(BN(y)) over groups of `pool` rows (pn2_utils.py:210-214, BatchNorm on the batch
+ * statistics mean / var): dh [groups * pool, C] = dout[g, c] on the first row of group g that attains the max when it is > 0,
+ * 0 elsewhere.  h is recomputed from y with pfpp_bn_apply's arithmetic.
+ * pfpp_bn_relu_bwd: backward of h = relu(BN_train(y)) (nn.BatchNorm2d in .train(), pn2_utils.py:211-213): dz = dh (h > 0);
+ * pass 1 reduces sum dz and sum dz xhat per channel over all rows in fp64 (dbeta += , dgamma += ), pass 2 writes
+ * dy = gamma / sqrt(var + eps) (dz - mean dz - xhat mean(dz xhat)).  dy may alias dh.  amax (optional, device [1]): max |dy|
+ * taken in the second pass (the gradient scale of the GEMMs that read dy).  C in {64, ..., 1024};
+ * workspace: pfpp_bn_relu_bwd_workspace(rows, C) bytes.
+ * pfpp_group_gather_bwd: backward of pfpp_group_gather's feature columns: dfeats [F, N, D] = sum over the slots (s, k) with
+ * idx[f, s, k] = p of dA[(f S + s) ns + k, :D]  (a gather per point, no float atomics; overwrites dfeats).                 */
+int pfpp_sa_pool_bwd(const float* y, int64_t groups, int64_t pool, int64_t C, int64_t ld, const float* mean, const float* var,
+                     const float* gamma, const float* beta, float eps, const float* dout, float* dh, pfpp_stream_t stream);
+int pfpp_bn_relu_bwd(const float* y, const float* dh, int64_t rows, int64_t C, int64_t ld, const float* mean, const float* var,
+                     const float* gamma, const float* beta, float eps, float* dgamma, float* dbeta, float* dy, float* amax,
+                     void* workspace, pfpp_stream_t stream);
+int64_t pfpp_bn_relu_bwd_workspace(int64_t rows, int64_t C);
+int pfpp_group_gather_bwd(const float* dA, int64_t lda, const int32_t* idx, float* dfeats, int64_t F, int64_t N, int64_t S,
+                          int64_t ns, int64_t D, pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -317,6 +317,14 @@ SIGNATURES = {
     "pfpp_verifier_head_bce": [_p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "pfpp_verifier_gelu_dropout": [_p, _p, _i64, _f32, _u64, _u32, _p],
     "pfpp_verifier_gelu_dropout_bwd": [_p, _p, _p, _i64, _f32, _u64, _u32, _p],
+    # ---- VQ-VAE pre-training (csrc/vqvae_train.hip)
+    "pfpp_chamfer_fwd": [_p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "pfpp_chamfer_bwd": [_p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p],
+    "pfpp_chamfer_reduce": [_p, _i64, _p, _i64, _f32, _p, _p],
+    "pfpp_vq_train": [_p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _p, _p, _p],
+    "pfpp_sa_pool_bwd": [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f32, _p, _p, _p],
+    "pfpp_bn_relu_bwd": [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _p],
+    "pfpp_group_gather_bwd": [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
@@ -335,6 +343,8 @@ PLAIN = {
     "pfpp_bn_stats_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_fragment_prepare_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_verifier_head_bce_workspace": ([], C.c_int64),
+    "pfpp_vq_train_workspace": ([_i64, _i64], C.c_int64),
+    "pfpp_bn_relu_bwd_workspace": ([_i64, _i64], C.c_int64),
 }
 
 # struct name in include/pfpp.h (without the pfpp_ prefix) -> its mirror here; load() compares the sizes

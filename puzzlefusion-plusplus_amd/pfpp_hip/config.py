@@ -30,6 +30,21 @@ def ae_config(**over) -> NS:
     return NS(**d)
 
 
+def vqvae_train_config(ae_name: str = "VQVAE", **over) -> NS:
+    """cfg of stage-1 pre-training (config/ae/global_config.yaml, vq_vae.yaml, model.yaml, data.yaml): .ae with its ae_name node,
+    .model.lr_scheduler (MultiStepLR [800, 1400], 0.5) and .data"""
+    target = {"VQVAE": "puzzlefusion_plusplus.vqvae.model.modules.vq_vae.VQVAE",
+              "PN2": "puzzlefusion_plusplus.vqvae.model.modules.pn2.PN2"}[ae_name]
+    ae = ae_config(**over.pop("ae", {}))
+    ae.ae_name = NS(_target_=target)
+    model = NS(lr_scheduler=NS(_target_="torch.optim.lr_scheduler.MultiStepLR", milestones=[800, 1400], gamma=0.5))
+    data = dict(batch_size=64, val_batch_size=64, num_workers=6, data_fn="everyday.{}.txt", data_dir="./data/pc_data/everyday/train/",
+                data_val_dir="./data/pc_data/everyday/val/", rot_range=-1, overfit=-1, num_pc_points=1000, min_num_part=2,
+                max_num_part=20, shuffle_parts=False, category="all")
+    data.update(over.pop("data", {}))
+    return NS(ae=ae, model=model, data=NS(**data), **over)
+
+
 def denoiser_model_config(**over) -> NS:
     d = dict(num_dim=64, num_point=25, out_channels=7, std=1, multires=10, embed_dim=512, num_layers=6, num_heads=8,
              dropout_rate=0.1, DDPM_TRAIN_STEPS=1000, DDPM_BETA_SCHEDULE="linear", timestep_spacing="leading",

@@ -1,13 +1,18 @@
 """VQ-VAE fragment encoder (drop-in for vqvae/model/modules/vq_vae.py and its duplicate
-denoiser/model/modules/encoder.py), HIP-backed.  state_dict keys: pn2.*, vector_quantization.*"""
+denoiser/model/modules/encoder.py), HIP-backed.  state_dict keys: pn2.*, vector_quantization.*
+
+encode / extract_features are the Denoiser's (frozen) feature extractor.  forward / decode / loss are stage-1 pre-training
+(vq_vae.py:24-50, 71-89): in .train() with autograd on, forward is one autograd node of pfpp_hip.vqvae_train whose backward takes
+the gradients of embedding_loss, pc_offset and z_q; gradients enter the encoder only through forward."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
 from pfpp_hip import encoder as hip_encoder
+from pfpp_hip import ops
 from pfpp_hip.packing import PackCache
-from puzzlefusion_plusplus.vqvae.model.modules.pn2 import PN2
+from puzzlefusion_plusplus.vqvae.model.modules.pn2 import PN2, train_engine_of, train_forward
 from puzzlefusion_plusplus.vqvae.model.modules.quantizer import VectorQuantizer
 
 
@@ -68,5 +73,34 @@ class VQVAE(nn.Module):
             pk = self.packed()
         return hip_encoder.extract_features(pk, part_pcs.contiguous(), pose.contiguous(), slot, self.cfg.ae.num_point)
 
+    def train_engine(self):
+        return train_engine_of(self)
+
     def decode(self, z_q):
-        raise NotImplementedError("decoder = VQ-VAE pre-training, out of scope of the HIP path")
+        """z_q [B,L,C] -> pc_offset [B,L,local_decode_pts,3] (vq_vae.py:71-72)"""
+        return self.pn2.decode(z_q)
+
+    def forward(self, data_dict, verbose=False):
+        """data_dict["part_pcs"] [F,N,3] -> {"embedding_loss", "pc_offset", "perplexity", "xyz", "z_q"} (vq_vae.py:24-50)"""
+        pcs = data_dict["part_pcs"]
+        if self.training:
+            emb, off, z_q, perp, xyz = train_forward(self, pcs)
+            return {"embedding_loss": emb, "pc_offset": off, "perplexity": perp, "xyz": xyz, "z_q": z_q}
+        from pfpp_hip.vqvae_train import vq_train
+
+        z_e, xyz = hip_encoder.pn2_encode(self.packed(), pcs.contiguous().float(), self.cfg.ae.num_point)
+        F, L, C = z_e.shape
+        cb = self.vector_quantization.embedding.weight.detach().contiguous()
+        slot = torch.arange(F, dtype=torch.int32, device=z_e.device)
+        z_q, codes = ops.vq_encode(z_e, cb, slot, F, return_codes=True)
+        vals, _, _ = vq_train(z_e.view(-1, cb.shape[1]), cb, codes.reshape(-1), self.vector_quantization.beta)
+        return {"embedding_loss": vals[0].reshape(()), "pc_offset": self.decode(z_q), "perplexity": vals[1].reshape(()), "xyz": xyz,
+                "z_q": z_q}
+
+    def loss(self, data_dict, output_dict):
+        """{"cd_loss", "embedding_loss"} (vq_vae.py:75-89); cd_loss is a differentiable HIP op (gradient to pc_offset)"""
+        from pfpp_hip.vqvae_train import chamfer_loss
+
+        ae = self.cfg.ae
+        cd = chamfer_loss(output_dict["pc_offset"], output_dict["xyz"], data_dict["part_pcs"], ae.num_point * ae.local_decode_pts)
+        return {"cd_loss": cd, "embedding_loss": output_dict["embedding_loss"]}
