@@ -1145,6 +1145,41 @@ int64_t pfpp_bn_relu_bwd_workspace(int64_t rows, int64_t C);
 int pfpp_group_gather_bwd(const float* dA, int64_t lda, const int32_t* idx, float* dfeats, int64_t F, int64_t N, int64_t S,
                           int64_t ns, int64_t D, pfpp_stream_t stream);
 
+/* ---- pc_data generation from fracture meshes (generate_pc_data.py:17-45; csrc/mesh_sample.hip) ----------------------------------
+ * Batch layout: CSR over the Pt parts of B puzzles, the parts of a puzzle contiguous and in slot order.  verts fp64 [V, 3],
+ * faces int32 [F, 3] (part-local vertex indices), vert_off / face_off int64 [Pt + 1], part_puzzle / part_slot int32 [Pt],
+ * puz_part_off int64 [B + 1], data_id int64 [B].  Data-dependent failures are not return codes of the launching calls (the
+ * kernels are only enqueued): they are recorded in `status`, one device uint64 the caller sets to all ones, and
+ * pfpp_mesh_status — the one entry here that waits for its stream — turns it into PFPP_EINVAL / PFPP_EUNSUPPORTED with
+ * pfpp_last_error naming the part or puzzle.
+ * pfpp_mesh_face_cdf: trimesh.sample.sample_surface's weights (vqvae/dataset/dataset.py:177): area [F] = |(b-a) x (c-a)| / 2 in
+ * fp64 (optional), cdf [F] = per-part inclusive prefix sum, total [Pt] = cdf of the part's last face.  A part whose total is 0 or
+ * not finite, or a face index outside its part, is an EINVAL.
+ * pfpp_mesh_sample_surface: sample_surface(mesh, N) per part (dataset.py:176-179): face = first j with cdf[j] >= u0 total
+ * (searchsorted side='left', clamped to F - 1), (l0, l1) -= 1 when l0 + l1 > 1, then |.|, p = ((b-a) l0 + (c-a) l1) + a.
+ * Uniforms u [Pt, N, 3] = (u0, l0, l1) when given; when u is NULL they are (pfpp_rng_u64(seed, split, idx) >> 11) 2^-53 with
+ * idx = ((data_id max_parts + slot) N + i) 3 + k.  points [Pt, N, 3] fp64; face_idx int32 [Pt, N], scale fp64 [Pt] (max - min
+ * over a part's coordinates, dataset.py:200) and ref_slot int32 [B] (first argmax of scale, :203) are optional.
+ * pfpp_mesh_vertex_graph: _check_connectivity (dataset.py:85-127): graph bool [B, max_parts, max_parts], parts i != j connected iff
+ * a vertex of i and one of j are equal after np.round(., 5), keys llrint(x 1e5).  max_parts <= 32.  A non-finite coordinate is an
+ * EINVAL; a puzzle whose keys span 2^21 or more on an axis (about 20.97 units) is an EUNSUPPORTED.
+ * pfpp_mesh_vertex_graph_workspace: from the per-puzzle vertex counts (host [B]) writes tab_off_host [B + 1] (the puzzles' hash
+ * table regions, power-of-two capacities >= 2 x vertex count; its device copy is the tab_off argument, S = tab_off_host[B]) and
+ * returns the workspace bytes, -1 on bad arguments.                                                                             */
+int pfpp_mesh_face_cdf(const double* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* face_off, int64_t Pt,
+                       double* area, double* cdf, double* total, uint64_t* status, pfpp_stream_t stream);
+int pfpp_mesh_sample_surface(const double* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* face_off,
+                             const double* cdf, const double* total, const int32_t* part_puzzle, const int32_t* part_slot,
+                             const int64_t* data_id, const int64_t* puz_part_off, int64_t Pt, int64_t B, int64_t N, const double* u,
+                             uint64_t seed, uint32_t split, int64_t max_parts, double* points, int32_t* face_idx, double* scale,
+                             int32_t* ref_slot, pfpp_stream_t stream);
+int64_t pfpp_mesh_vertex_graph_workspace(const int64_t* puzzle_nverts_host, int64_t B, int64_t* tab_off_host);
+int pfpp_mesh_vertex_graph(const double* verts, const int64_t* vert_off, const int32_t* part_puzzle, const int32_t* part_slot,
+                           const int64_t* puz_part_off, const int64_t* tab_off, int64_t Pt, int64_t B, int64_t V, int64_t S,
+                           int64_t max_parts, uint8_t* graph, void* workspace, int64_t workspace_bytes, uint64_t* status,
+                           pfpp_stream_t stream);
+int pfpp_mesh_status(const uint64_t* status, pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,15 @@ __host__ __device__ __forceinline__ uint32_t pfpp_rng_u32(uint64_t seed, uint32_
   z ^= z >> 31;
   return (uint32_t)(z >> 32);
 }
+// the full 64-bit word of the same finaliser (mesh surface sampling, csrc/mesh_sample.hip: u = (z >> 11) 2^-53)
+__host__ __device__ __forceinline__ uint64_t pfpp_rng_u64(uint64_t seed, uint32_t site, uint64_t idx) {
+  uint64_t z = seed ^ ((uint64_t)site * 0xD6E8FEB86659FD93ull);
+  z += (idx + 1) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
 // keep threshold for drop probability p: keep iff rng >= thresh
 inline uint32_t pfpp_drop_thresh(float p) {
   const double t = (double)p * 4294967296.0;

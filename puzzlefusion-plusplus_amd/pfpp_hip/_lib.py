@@ -325,6 +325,11 @@ SIGNATURES = {
     "pfpp_sa_pool_bwd": [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f32, _p, _p, _p],
     "pfpp_bn_relu_bwd": [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _p],
     "pfpp_group_gather_bwd": [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _p],
+    # ---- pc_data generation from fracture meshes (csrc/mesh_sample.hip)
+    "pfpp_mesh_face_cdf": [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _p],
+    "pfpp_mesh_sample_surface": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _u64, _u32, _i64, _p, _p, _p, _p, _p],
+    "pfpp_mesh_vertex_graph": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p],
+    "pfpp_mesh_status": [_p, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
@@ -345,6 +350,7 @@ PLAIN = {
     "pfpp_verifier_head_bce_workspace": ([], C.c_int64),
     "pfpp_vq_train_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_bn_relu_bwd_workspace": ([_i64, _i64], C.c_int64),
+    "pfpp_mesh_vertex_graph_workspace": ([_p, _i64, _p], C.c_int64),
 }
 
 # struct name in include/pfpp.h (without the pfpp_ prefix) -> its mirror here; load() compares the sizes
