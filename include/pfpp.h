@@ -1180,6 +1180,41 @@ int pfpp_mesh_vertex_graph(const double* verts, const int64_t* vert_off, const i
                            pfpp_stream_t stream);
 int pfpp_mesh_status(const uint64_t* status, pfpp_stream_t stream);
 
+/* ---- matcher back end: descriptors -> matching_data (Jigsaw_matching/; csrc/matching.hip) ---------------------------------------
+ * Batch layout: the points of all puzzles flat, [N, 128] descriptors / [N, 3] coordinates; piece_off int64 [Pt + 1] are the point
+ * offsets of the Pt pieces (the pieces of a puzzle contiguous and in slot order, empty slots as empty ranges), puz_piece_off int64
+ * [B + 1] the piece ranges of the puzzles.  Nothing is padded to the largest puzzle.
+ * pfpp_match_classify_compact (model/jigsaw/joint_seg_align_model.py:164-170 + utils/critical_pcs.py:4-18): logit = bias + sum_k
+ * relu(x_k scale_k + shift_k) w_k (BatchNorm1d in eval folded to scale / shift), label = fp32 sigmoid(logit) > 0.5; then per piece
+ * the local indices of its labelled points in ascending order at the piece's offset of critical_pcs_idx [N] (zero behind them)
+ * and their count in n_critical_pcs [Pt].  With labels_in (uint8 [N]) the classifier is skipped and those labels are compacted
+ * (compute_label's path, :203-219); labels (uint8 [N], optional) receives the labels used.  C = 128.
+ * pfpp_match_gather_rows (:110-116, :234 first two layers): out [R, 128] = relu(BatchNorm(feats[critical rows])) in piece order,
+ * row_piece int32 [R] = piece_slot of the row's piece; crit_off int64 [Pt + 1] = exclusive prefix sum of n_critical_pcs, R =
+ * crit_off[Pt].
+ * pfpp_match_normalize_halves (:237-247): F.normalize(p = 2, eps = 1e-12) of x[:, :256] and x[:, 256:], in place.  D = 512.
+ * pfpp_sinkhorn_masked (:251-268, utils/linear_solvers.py:9-247 per-sample branch, one puzzle): s [n, n] (row stride ld), piece
+ * int32 [n]; L = s / tau in fp32; potentials u, v fp64 [n] start at 0; iteration k even: u_i += LSE_j((L_ij - u_i) - v_j), odd: the same for
+ * v_j over i, both over the entries whose row and column pieces differ (the reference's -1e6 mask contributes exp(-2e7) = 0);
+ * ds_mat [n, n] = exp((L - u) - v), exactly 0 where the pieces are equal.  The matrix is only read; column sweeps go through
+ * workspace partials folded in a fixed order, so two runs agree bitwise.  workspace: pfpp_sinkhorn_workspace(n) bytes (-1 for
+ * n outside [0, 65535]).  A puzzle in which fewer than two pieces have rows is the caller's to skip (every entry masked).
+ * pfpp_fracture_labels (:465-484): dist[i] = sqrt(max(min_j |p_i - p_j|^2, 1e-12)) over the points j of the OTHER pieces of i's
+ * puzzle (pfpp_nn_dist's arithmetic; inf when there is none), labels[i] = dist[i] < thresholds[i].  max_points = the largest
+ * puzzle's point count; dist is optional.                                                                                      */
+int pfpp_match_classify_compact(const float* feats, const float* bn_scale, const float* bn_shift, const float* w, float bias,
+                                const uint8_t* labels_in, const int64_t* piece_off, int64_t Pt, int64_t C, float* logits,
+                                uint8_t* labels, int64_t* critical_pcs_idx, int64_t* n_critical_pcs, pfpp_stream_t stream);
+int pfpp_match_gather_rows(const float* feats, const float* bn_scale, const float* bn_shift, const int64_t* critical_pcs_idx,
+                           const int64_t* piece_off, const int64_t* crit_off, const int32_t* piece_slot, int64_t Pt, int64_t R,
+                           int64_t C, float* out, int32_t* row_piece, pfpp_stream_t stream);
+int pfpp_match_normalize_halves(float* x, int64_t R, int64_t D, pfpp_stream_t stream);
+int64_t pfpp_sinkhorn_workspace(int64_t n);
+int pfpp_sinkhorn_masked(const float* s, int64_t ld, const int32_t* piece, int64_t n, float tau, int64_t max_iter, double* u, double* v,
+                         float* ds_mat, void* workspace, int64_t workspace_bytes, pfpp_stream_t stream);
+int pfpp_fracture_labels(const float* gt_pcs, const int64_t* piece_off, const int64_t* puz_piece_off, const float* thresholds,
+                         int64_t B, int64_t max_points, float* dist, uint8_t* labels, pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -330,6 +330,12 @@ SIGNATURES = {
     "pfpp_mesh_sample_surface": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _u64, _u32, _i64, _p, _p, _p, _p, _p],
     "pfpp_mesh_vertex_graph": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p],
     "pfpp_mesh_status": [_p, _p],
+    # ---- matcher back end (csrc/matching.hip)
+    "pfpp_match_classify_compact": [_p, _p, _p, _p, _f32, _p, _p, _i64, _i64, _p, _p, _p, _p, _p],
+    "pfpp_match_gather_rows": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p],
+    "pfpp_match_normalize_halves": [_p, _i64, _i64, _p],
+    "pfpp_sinkhorn_masked": [_p, _i64, _p, _i64, _f32, _i64, _p, _p, _p, _p, _i64, _p],
+    "pfpp_fracture_labels": [_p, _p, _p, _p, _i64, _i64, _p, _p, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
@@ -351,6 +357,7 @@ PLAIN = {
     "pfpp_vq_train_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_bn_relu_bwd_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_mesh_vertex_graph_workspace": ([_p, _i64, _p], C.c_int64),
+    "pfpp_sinkhorn_workspace": ([_i64], C.c_int64),
 }
 
 # struct name in include/pfpp.h (without the pfpp_ prefix) -> its mirror here; load() compares the sizes

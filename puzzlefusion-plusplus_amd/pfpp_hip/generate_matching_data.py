@@ -1,0 +1,100 @@
+"""matching_data from per-point descriptors on one GPU — the back half of the reference's matcher (Jigsaw_matching/, test run)
+
+    python -m pfpp_hip.generate_matching_data --features DIR --checkpoint CKPT --out DIR [--batch-size 16] [--gemm f32|f16x3]
+
+reads one DIR/<data_id>.npz per puzzle (part_feats float32 [N_sum, 128], gt_pcs float32 [N_sum, 3], n_pcs int64 [P], part_valids
+[P]: the seam the descriptor network feeds), runs pfpp_hip.matching.MatchingHead in batches and writes
+OUT/<data_id>.npz through pfpp_hip.io.save_matching_data.  A file that exists is left alone and its puzzle is not computed."""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import time
+from typing import List, Optional
+
+FEATURE_KEYS = ("part_feats", "gt_pcs", "n_pcs", "part_valids")
+
+
+def list_puzzles(features: str, out: str):
+    """-> (data ids still to do, ids skipped because their file exists); a file name that is not <integer>.npz is an error"""
+    todo, skipped = [], []
+    for name in sorted(os.listdir(features)):
+        if not name.endswith(".npz"):
+            continue
+        stem = name[:-4]
+        if not stem.isdigit():
+            raise ValueError(f"{os.path.join(features, name)}: feature files are named <data_id>.npz")
+        (skipped if os.path.exists(os.path.join(out, f"{int(stem)}.npz")) else todo).append(int(stem))
+    return sorted(todo), sorted(skipped)
+
+
+def load_features(features: str, data_id: int):
+    import numpy as np
+
+    path = os.path.join(features, f"{data_id}.npz")
+    with np.load(path) as d:
+        missing = [k for k in FEATURE_KEYS if k not in d.files]
+        if missing:
+            raise KeyError(f"{path}: missing entries {missing}")
+        x = {k: d[k] for k in FEATURE_KEYS}
+    n = int(np.asarray(x["n_pcs"]).sum())
+    if x["part_feats"].shape != (n, 128) or x["gt_pcs"].shape != (n, 3) or x["n_pcs"].shape != x["part_valids"].shape:
+        raise ValueError(f"{path}: part_feats {x['part_feats'].shape}, gt_pcs {x['gt_pcs'].shape} do not match n_pcs (sum {n})")
+    return x
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m pfpp_hip.generate_matching_data", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--features", required=True, help="directory of <data_id>.npz descriptor files")
+    ap.add_argument("--checkpoint", required=True, help="Jigsaw checkpoint (Lightning file or bare state_dict)")
+    ap.add_argument("--out", required=True, help="matching_data directory")
+    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--gemm", choices=("f32", "f16x3"), default="f32")
+    args = ap.parse_args(argv)
+    if args.batch_size < 1:
+        ap.error("--batch-size must be at least 1")
+    if not os.path.isdir(args.features):
+        ap.error(f"--features {args.features}: not a directory")
+    if not os.path.isfile(args.checkpoint):
+        ap.error(f"--checkpoint {args.checkpoint}: no such file")
+    todo, skipped = list_puzzles(args.features, args.out)
+    if skipped:
+        print(f"{len(skipped)} puzzles already in {args.out}: left alone", flush=True)
+    if not todo:
+        print("nothing to do", flush=True)
+        return 0
+
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        print("generate_matching_data: no GPU: the matching kernels run on the GPU only", file=sys.stderr)
+        return 2
+    from pfpp_hip.matching import MatchingHead, match_edges, write_matching_data
+
+    head = MatchingHead.from_checkpoint(args.checkpoint, gemm_mode=args.gemm).cuda()
+    t0, n, host = time.perf_counter(), 0, 0.0
+    for i in range(0, len(todo), args.batch_size):
+        ids = todo[i:i + args.batch_size]
+        items = [load_features(args.features, d) for d in ids]
+        P = max(x["n_pcs"].shape[0] for x in items)
+        pad = lambda a: np.concatenate([np.asarray(a).reshape(-1), np.zeros(P - a.shape[0], dtype=a.dtype)])
+        out = head([torch.from_numpy(np.ascontiguousarray(x["part_feats"], dtype=np.float32)).cuda() for x in items],
+                   np.stack([pad(x["n_pcs"].astype(np.int64)) for x in items]), np.stack([pad(x["part_valids"].astype(np.float32)) for x in items]),
+                   dense_perm=False)
+        host += out.timings["host_assignment_s"]
+        nc = out.n_critical_pcs.cpu().numpy()
+        for b, (d, x) in enumerate(zip(ids, items)):
+            p = x["n_pcs"].shape[0]
+            edges, corr = match_edges(out.perm_mat[b], nc[b], int(np.asarray(x["part_valids"]).sum()))
+            write_matching_data(args.out, d, edges=edges, correspondence=corr, gt_pcs=x["gt_pcs"], critical_pcs_idx=out.critical_pcs_idx[b],
+                                n_pcs=x["n_pcs"], n_critical_pcs=nc[b, :p])
+            n += 1
+    dt = time.perf_counter() - t0
+    print(f"{n} puzzles -> {args.out} in {dt:.2f} s ({n / max(dt, 1e-9):.1f} files/s; host assignment {host:.2f} s)", flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
