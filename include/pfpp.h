@@ -1215,6 +1215,37 @@ int pfpp_sinkhorn_masked(const float* s, int64_t ld, const int32_t* piece, int64
 int pfpp_fracture_labels(const float* gt_pcs, const int64_t* piece_off, const int64_t* puz_piece_off, const float* thresholds,
                          int64_t B, int64_t max_points, float* dist, uint8_t* labels, pfpp_stream_t stream);
 
+/* ---- matcher front end: ragged PointNet++ encoder (Jigsaw_matching/model/modules/encoder/pointnet2_pointwise/; csrc/pointnet_ragged.hip)
+ * Layout: the points of all pieces of all puzzles flat, [N, 3]; a level is described by CSR offsets int64 [P + 1] over the P pieces.
+ * Which puzzle a piece belongs to plays no part (the reference asserts one puzzle per call, pointnet2_dynamic_utils.py:122).
+ * pfpp_ragged_fps (torch_cluster.fps(x, batch, ratio, random_start) as called at pointnet2_dynamic_utils.py:123, for the L levels of
+ * pointnet2_msg.py:82-85 in one launch): level_off int64 [L + 1, P + 1], row 0 the input points, row l the centroids of level l (the
+ * caller's counts: ceil(fl32(fl32(ratio) fl32(n))) per piece); start int64 [L, P] the local first index per level and piece.  Level l
+ * samples the centroids of level l - 1.  pfpp_fps_start's arithmetic: d = (dx dx + dy dy) + dz dz in fp32 without contraction, running
+ * minimum, first argmax.  idx int64 / new_xyz float: the levels one behind the other (level l at row sum_{j<l} level_off[j + 1][P]);
+ * an index is global in the flat array of the level it samples from, pieces in order, selection order inside a piece.
+ * max_n = the largest piece (<= 8192 points).
+ * pfpp_ragged_knn (knn(x, y, k, batch_x, batch_y) + to_dense_batch(fill_value) + the group_first fix-up, :131-136 and :197-205): for each
+ * of the M queries (CSR query_off over the same P pieces) the min(K, n_piece) nearest of its piece's points by (dx dx + dy dy) + dz dz,
+ * ascending, ties to the lower index, as global indices int32 [M, K]; the remaining slots repeat the first.  count int32 [M] (optional)
+ * receives min(K, n_piece).  K = 3, 16 or 32; N = number of points.
+ * pfpp_ragged_group (:138-146): out row (s, j), j < pool, = [ feats[g, 0:D] | xyz[g] - new_xyz[s] | 0 ] with g = idx[s ldi + j mod K]: the
+ * column order of pfpp_group_gather; `pool` rows per centroid (pool % K == 0: a K = 16 scale fills a max-pool of 32 with duplicates).
+ * pfpp_ragged_interp (PointNetFeaturePropagationDynamic.forward :191-217): out [N, ldo] row i = [ points1[i, 0:D1] | sum_j w_j
+ * points2[idx[i, j]] ], w_j = r_j / ((r_0 + r_1) + r_2), r_j = 1 / (d_j + 1e-8), d_j = sum over the coordinates in order of
+ * (a a + b b) - (2 a) b (a = xyz1[i], b = xyz2[idx[i, j]]; fp32, no contraction) for j < count[i] and 1e8 behind; idx / count are
+ * pfpp_ragged_knn's with K = 3.  S == 1 is the reference's broadcast of the one centroid (:191-192; idx / count unused).  weights
+ * [N, 3] (optional) receives w.  D1, D2, ldo multiples of 4, rows 16-byte aligned.                                               */
+int pfpp_ragged_fps(const float* xyz, const int64_t* level_off, const int64_t* start, int64_t P, int64_t L, int64_t max_n,
+                    int64_t* idx, float* new_xyz, pfpp_stream_t stream);
+int pfpp_ragged_knn(const float* pts, const int64_t* pts_off, const float* queries, const int64_t* query_off, int64_t P, int64_t M,
+                    int64_t N, int64_t K, int32_t* idx, int32_t* count, pfpp_stream_t stream);
+int pfpp_ragged_group(const float* feats, int64_t ldf, int64_t D, const float* xyz, const float* new_xyz, const int32_t* idx,
+                      int64_t ldi, int64_t K, int64_t pool, int64_t S, float* out, int64_t ldo, pfpp_stream_t stream);
+int pfpp_ragged_interp(const float* xyz1, const float* xyz2, const int32_t* idx, const int32_t* count, const float* points2, int64_t D2,
+                       const float* points1, int64_t D1, int64_t N, int64_t S, float* out, int64_t ldo, float* weights,
+                       pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -336,6 +336,11 @@ SIGNATURES = {
     "pfpp_match_normalize_halves": [_p, _i64, _i64, _p],
     "pfpp_sinkhorn_masked": [_p, _i64, _p, _i64, _f32, _i64, _p, _p, _p, _p, _i64, _p],
     "pfpp_fracture_labels": [_p, _p, _p, _p, _i64, _i64, _p, _p, _p],
+    # ---- matcher front end: ragged PointNet++ encoder (csrc/pointnet_ragged.hip)
+    "pfpp_ragged_fps": [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p],
+    "pfpp_ragged_knn": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p],
+    "pfpp_ragged_group": [_p, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p],
+    "pfpp_ragged_interp": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
