@@ -312,8 +312,8 @@ int pfpp_gemm_planes(const pfpp_gemm_planes_args* args, pfpp_stream_t stream);
  * are k-major fp16 planes read in place (leading dimensions M and N; scales folded out: gw += dY^T.X / (dy.scale * x.scale),
  * gb += colsum(dY) / dy.scale; gb may be NULL).  Every output tile runs the whole contraction in one accumulator chain (no K split,
  * no workspace, no reduction launch; deterministic); the problems' tiles are dealt to the XCDs as one concatenated list.
- * variant: 0 = the library's choice (= 2: 256 x 128 tiles, 160 workgroups for a block's six problems, unless the environment
- * names another one in PFPP_DW_GROUP_VARIANT); alternatives: 3 = 128 x 128 tiles, 6 / 7 = 128 x 64 (three / two stages).       */
+ * variant: 0 = the library's choice (= 2: 256 x 128 tiles, 160 workgroups for a block's six problems); alternatives:
+ * 3 = 128 x 128 tiles, 6 / 7 = 128 x 64 (three / two stages).       */
 #define PFPP_DW_GROUP_MAX 8
 typedef struct pfpp_dw_job {
   pfpp_planes dy;      /* [K, M] */
@@ -323,8 +323,10 @@ typedef struct pfpp_dw_job {
   int64_t M, N;
 } pfpp_dw_job;
 int pfpp_gemm_dw_group(const pfpp_dw_job* jobs, int32_t n_jobs, int64_t K, int32_t variant, pfpp_stream_t stream);
-/* name of the kernel instantiation the calling thread's last pfpp_gemm / pfpp_gemm_planes call launched through the plane
- * path ("" when that call took another kernel): lets a profiler-side tool attribute event timings to kernel names */
+/* name of the kernel instantiation the calling thread's last pfpp_gemm, pfpp_gemm_planes, pfpp_gemm_dw_group, pfpp_gemm_grad or
+ * pfpp_gemm_grad_group call launched ("" after a pfpp_gemm call that launched nothing; "+pl_reduce_kernel" appended where a slab
+ * reduction followed): lets a profiler-side tool attribute event timings to kernel names.  gemm_pl_kernel's eighth field is a
+ * constant 0 (a template parameter that no longer exists; the positions of the others are kept) */
 const char* pfpp_last_gemm_kernel(void);
 
 /* ---- a4 + a5 + a6 fused, for a set-abstraction level without input features ---------------------------

@@ -747,12 +747,7 @@ static int attn_dense_impl(const float* qkv, float* out, _Float16* out_hi, _Floa
   const int short_max = short_env ? atoi(short_env) : 512;
   if (dh == 64 && f16x3 && !lse && max_len <= short_max && (int64_t)grid.x * H * n_seq <= 64) {
     constexpr size_t smem = (size_t)4 * (2 * 32 * (64 + 8) + 2 * 64 * (32 + 8)) * sizeof(_Float16) + (size_t)(4 * 32 * (64 + 4) + 8 * 32) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)attn_dense_short_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return pfpp::check_launch("pfpp_attn_dense");
-      attr_set = true;
-    }
+    if (pfpp_allow_dyn_lds<attn_dense_short_kernel<64>>((int)smem) != hipSuccess) return pfpp::check_launch("pfpp_attn_dense");
     const dim3 g32((unsigned)((max_len + 31) / 32), (unsigned)H, (unsigned)n_seq);
     hipLaunchKernelGGL(attn_dense_short_kernel<64>, g32, dim3(256), smem, st, qkv, out, out_hi, out_lo, seq_off, seq_len, key_valid, kv_stride,
                        (int)H, scale);

@@ -104,12 +104,7 @@ extern "C" int pfpp_edge_histogram(const float* pts, const int32_t* idx_a, const
   PFPP_SUPPORTED(max_m >= 0 && max_m <= 6000, "more than 6000 correspondences on one edge");
   if (n_edges == 0) return PFPP_OK;
   const size_t smem = (size_t)6 * (max_m > 0 ? max_m : 1) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(edge_histogram_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 6 * 6000 * 4);
-    attr_set = true;
-  }
+  (void)pfpp_allow_dyn_lds<edge_histogram_kernel>(6 * 6000 * 4);
   hipLaunchKernelGGL(edge_histogram_kernel, dim3((unsigned)n_edges), dim3(256), smem, pfpp::as_stream(stream), pts,
                      idx_a, idx_b, edge_off, hist, (int)max_m);
   return pfpp::check_launch(__func__);

@@ -23,13 +23,12 @@
 // results are discarded) instead of predicated.  LDS rows are padded (36 floats / 40 halfs) so
 // that the 16-byte fragment reads are bank-conflict free.  Tile ids are remapped XCD-aware.
 #include <string.h>
-#include <stdlib.h>
 
 #include "gemm_common.h"
 
 namespace pfpp_gemm_detail {
-int launch_f16x3_planes(const GemmP& p, int batch, hipStream_t st, int group_m, int variant);   // gemm_pl.hip
-int launch_f16x3_planes_af32(const GemmP& p, int batch, hipStream_t st, int group_m);
+int launch_f16x3_planes(const GemmP& p, int batch, hipStream_t st);   // gemm_pl.hip
+int launch_f16x3_planes_af32(const GemmP& p, int batch, hipStream_t st);
 }
 
 namespace {
@@ -38,13 +37,6 @@ using namespace pfpp_gemm_detail;
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-
-// Diagnostic builds only (tools/diag/gemm_ablate.py): remove one ingredient of the K loop to see what bounds it.
-//   1 = no global loads after the first tile   2 = no MFMAs   3 = no fragment reads from LDS   4 = no LDS stores / splits
-//   5 = 1 + 4 (fragment reads + MFMAs + barrier only)   6 = 5 without the barrier
-#ifndef PFPP_ABLATE
-#define PFPP_ABLATE 0
-#endif
 
 constexpr int BK = 32;
 constexpr int LDS_LD = BK + 4;   // fp32 path: 36 floats = 144 B rows
@@ -266,11 +258,10 @@ __device__ __forceinline__ void split4(const float4 v, half4& hi, half4& lo) {
 
 // AFF (PF2 variants only): the A operand always carries the fused BatchNorm+ReLU affine — a compile-time property there,
 // because a data-dependent branch in the K loop splits the scheduling region the two-deep prefetch relies on
-// APRE: the A operand arrives as pre-split fp16 planes (p.Ahi / p.Alo, written by the producing kernel's epilogue): it is
-// staged exactly like a pre-split W — 16-byte loads, 16-byte LDS stores, no conversion instructions in the K loop
+// (a pre-split A operand — p.Ahi / p.Alo — never comes here: pfpp_gemm sends it to the plane kernel, gemm_pl.hip)
 // PFD > 2: `PFD` K-tiles in flight in registers (latency-bound launches: a handful of workgroups, each walking its K range
 // alone — the sampler step of a single puzzle, 250 rows): generalisation of the two-deep loop, PFD tiles per branch-free trip
-template <int MT, int NT, bool WPRE, int WM, int WN, bool PF2, bool AFF, bool APRE, int PFD = 0>
+template <int MT, int NT, bool WPRE, int WM, int WN, bool PF2, bool AFF, int PFD = 0>
 __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
   constexpr int NTHR = 64 * WM * WN;
   constexpr int BM = 32 * MT * WM;
@@ -312,14 +303,10 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
   // ---- staging registers and (clamped) source rows ---------------------------------------------
   constexpr int NWF = WPRE ? 1 : WF_IT;
   constexpr int NWH = WPRE ? WH_IT : 1;
-  constexpr int AH_IT = BM / (NTHR / 4);   // 16-byte (8-half) loads per thread and plane for a pre-split A
-  constexpr int NAF = APRE ? 1 : A_IT;
-  constexpr int NAH = APRE ? AH_IT : 1;
   // one set of staging registers per K-tile in flight (PF2: two sets = prefetch distance 2, for grids of one or two
   // workgroups per CU where nothing else hides the load latency)
   struct Stage {
-    float4 ra[NAF];
-    uint4 rah[NAH], ral[NAH];
+    float4 ra[A_IT];
     float4 rwf[NWF];
     uint4 rwh[NWH], rwl[NWH];
     float4 r_mul, r_add;      // fused BN+ReLU on A
@@ -331,7 +318,7 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
   // the fused-BatchNorm operand is a run-time property only of the small one-deep tiles (set abstraction 1 in train mode);
   // everywhere else it is a template parameter (AFF) or absent — a data-dependent branch in the K loop costs the whole
   // loop its scheduling freedom (the 256x256 kernel's steady state had four of them)
-  constexpr bool RT_AFF = !PF2 && !APRE && PFD == 0 && (MT * NT <= 4);
+  constexpr bool RT_AFF = !PF2 && PFD == 0 && (MT * NT <= 4);
   const bool a_aff = RT_AFF && p.a_mul != nullptr;
   // staging rows: bits 0 and 2 of the row index are swapped, so the two rows a 16-lane (8-byte stores) or 8-lane
   // (16-byte stores) LDS store group touches are 4 apart — with 80-byte rows their bank ranges are then disjoint
@@ -339,21 +326,10 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
   auto swap02 = [](int r) { return (r & ~5) | ((r & 1) << 2) | ((r >> 2) & 1); };
   const int a_row = swap02(tid >> 3), a_c4 = tid & 7;
   const int h_row = swap02(tid >> 2), h_c8 = tid & 3;    // pre-split W: 4 lanes x 8 halfs cover a 32-half row slice
-  const float* a_ptr[NAF];
-  const _Float16* ah_ptr[NAH];
-  const _Float16* al_ptr[NAH];
+  const float* a_ptr[A_IT];
   const float* wf_ptr[NWF];
   const _Float16* wh_ptr[NWH];
   const _Float16* wl_ptr[NWH];
-  if constexpr (APRE) {
-    const int64_t a_off = z0 * p.sA0 + z1 * p.sA1;
-#pragma unroll
-    for (int it = 0; it < AH_IT; ++it) {
-      const int gm = min(m0 + h_row + (NTHR / 4) * it, p.M - 1);
-      ah_ptr[it] = reinterpret_cast<const _Float16*>(p.Ahi) + a_off + (int64_t)gm * p.lda + h_c8 * 8;
-      al_ptr[it] = reinterpret_cast<const _Float16*>(p.Alo) + a_off + (int64_t)gm * p.lda + h_c8 * 8;
-    }
-  } else
 #pragma unroll
   for (int it = 0; it < A_IT; ++it) {
     const int gm = min(m0 + a_row + (NTHR / 8) * it, p.M - 1);
@@ -380,20 +356,9 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
     }
   }
   auto load_full = [&](Stage& s, int k0) {
-#if PFPP_ABLATE == 1 || PFPP_ABLATE == 5 || PFPP_ABLATE == 6
-    if (k0 != 0) return;
-#endif
-    if constexpr (APRE) {
 #pragma unroll
-      for (int it = 0; it < AH_IT; ++it) {
-        s.rah[it] = *reinterpret_cast<const uint4*>(ah_ptr[it] + k0);
-        s.ral[it] = *reinterpret_cast<const uint4*>(al_ptr[it] + k0);
-      }
-    } else {
-#pragma unroll
-      for (int it = 0; it < A_IT; ++it) s.ra[it] = *reinterpret_cast<const float4*>(a_ptr[it] + k0);
-    }
-    if (!APRE && (AFF || (RT_AFF && a_aff))) {
+    for (int it = 0; it < A_IT; ++it) s.ra[it] = *reinterpret_cast<const float4*>(a_ptr[it] + k0);
+    if (AFF || (RT_AFF && a_aff)) {
       s.r_mul = *reinterpret_cast<const float4*>(p.a_mul + k0 + a_c4 * 4);
       s.r_add = *reinterpret_cast<const float4*>(p.a_add + k0 + a_c4 * 4);
     }
@@ -409,10 +374,7 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
     }
   };
   auto load_tail = [&](Stage& s, int k0) {
-    if constexpr (APRE) {        // pre-split A needs K % 32 == 0 (validated on the host): there is no ragged tile
-#pragma unroll
-      for (int it = 0; it < AH_IT; ++it) { s.rah[it] = make_uint4(0, 0, 0, 0); s.ral[it] = make_uint4(0, 0, 0, 0); }
-    } else if (p.g_idx) {
+    if (p.g_idx) {
       // fused grouping: the last 4 columns are the neighbour's offset from its centroid (+ a zero); recomputed from
       // the row index here so that nothing extra stays live across the K loop
 #pragma unroll
@@ -448,20 +410,9 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
     }
   };
   auto store_tiles = [&](const Stage& s, int buf, int part = 2) {      // part 0: A planes, 1: W planes, 2: both
-#if PFPP_ABLATE == 4 || PFPP_ABLATE == 5 || PFPP_ABLATE == 6
-    if (buf >= 0) return;
-#endif
     _Float16* st = gemm_smem_h + buf * STAGE;
     _Float16* ahi = st, *alo = st + PLANE_A, *whi = st + 2 * PLANE_A, *wlo = st + 2 * PLANE_A + PLANE_W;
-    if constexpr (APRE) {
-      if (part != 1)
-#pragma unroll
-        for (int it = 0; it < AH_IT; ++it) {
-          const int off = (h_row + (NTHR / 4) * it) * LDH + h_c8 * 8;
-          *reinterpret_cast<uint4*>(ahi + off) = s.rah[it];
-          *reinterpret_cast<uint4*>(alo + off) = s.ral[it];
-        }
-    } else if (part != 1)
+    if (part != 1)
 #pragma unroll
     for (int it = 0; it < A_IT; ++it) {
       half4 hi, lo;
@@ -499,55 +450,14 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
     const _Float16* st = gemm_smem_h + buf * STAGE;
     const _Float16* a_base = st + (wm * 32 * MT + l31) * LDH + lhi * 8;
     const _Float16* w_base = st + 2 * PLANE_A + (wn * 32 * NT + l31) * LDH + lhi * 8;
-#ifndef PFPP_HOIST
-#define PFPP_HOIST 0     // experiment (tools/diag/gemm_ablate.py): isolated GEMMs +0..10 % at 3850 rows, -4 % at 16000x1536x512;
-                         // whole-step timings unchanged within noise, so the simpler loop stays
-#endif
-    if constexpr (PFPP_HOIST && MT == 2) {
-      // all fragment reads of the K-tile up front: the second 16-deep step's reads land behind the first step's MFMAs
-      half8 fa_h[2][MT], fa_l[2][MT], fb_h[2][NT], fb_l[2][NT];
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          fa_h[ks][i] = *reinterpret_cast<const half8*>(a_base + i * 32 * LDH + ks * 16);
-          fa_l[ks][i] = *reinterpret_cast<const half8*>(a_base + PLANE_A + i * 32 * LDH + ks * 16);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          fb_h[ks][j] = *reinterpret_cast<const half8*>(w_base + j * 32 * LDH + ks * 16);
-          fb_l[ks][j] = *reinterpret_cast<const half8*>(w_base + PLANE_W + j * 32 * LDH + ks * 16);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_l[ks][i], fb_h[ks][j], accM[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_h[ks][i], fb_l[ks][j], accM[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_h[ks][i], fb_h[ks][j], accM[i][j], 0, 0, 0);
-      }
-      return;
-    }
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) {
       if (ks < ks_begin || ks >= ks_end) continue;
       half8 bh[NT], bl[NT];
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-#if PFPP_ABLATE == 3
-        bh[j] = bl[j] = half8{(_Float16)(lane + j), 1, 2, 3, 4, 5, 6, 7};
-#else
         bh[j] = *reinterpret_cast<const half8*>(w_base + j * 32 * LDH + ks * 16);
         bl[j] = *reinterpret_cast<const half8*>(w_base + PLANE_W + j * 32 * LDH + ks * 16);
-#endif
       }
       // A fragments two M-tiles at a time (keeps the 128x64 wave tile of the 256x256 variant in registers)
 #pragma unroll
@@ -555,22 +465,11 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
         half8 ah[IB], al[IB];
 #pragma unroll
         for (int ii = 0; ii < IB; ++ii) {
-#if PFPP_ABLATE == 3
-          ah[ii] = al[ii] = half8{(_Float16)(lane + ii + ks), 1, 2, 3, 4, 5, 6, 7};
-#else
           ah[ii] = *reinterpret_cast<const half8*>(a_base + (i0 + ii) * 32 * LDH + ks * 16);
           al[ii] = *reinterpret_cast<const half8*>(a_base + PLANE_A + (i0 + ii) * 32 * LDH + ks * 16);
-#endif
         }
         // term-major order: the three MFMAs that feed one accumulator are 2*NT instructions apart, never back to back
         // (a dependent MFMA on the same accumulator waits for the previous one's passes; small terms first)
-#if PFPP_ABLATE == 2
-#pragma unroll
-        for (int ii = 0; ii < IB; ++ii)
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            accM[i0 + ii][j][0] += (float)al[ii][0] * (float)bh[j][0] + (float)ah[ii][1] * (float)bl[j][1];
-#else
 #pragma unroll
         for (int ii = 0; ii < IB; ++ii)
 #pragma unroll
@@ -586,7 +485,6 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
 #pragma unroll
           for (int j = 0; j < NT; ++j)
             accM[i0 + ii][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ii], bh[j], accM[i0 + ii][j], 0, 0, 0);
-#endif
       }
     }
   };
@@ -641,9 +539,7 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
       load_full(s0, kb + (kt + 1) * BK);
       compute(kt & 1);
       store_tiles(s0, (kt & 1) ^ 1);
-#if PFPP_ABLATE != 6
       __syncthreads();
-#endif
     }
     for (; kt < nk; ++kt) {
       const bool has_next = kt + 1 < nk;
@@ -739,110 +635,148 @@ __device__ __forceinline__ void gemm_f16x3_body(const GemmP& p) {
 
 template <int MT, int NT, bool WPRE, int WM = 2, int WN = 2, bool PF2 = false, bool AFF = false>
 __global__ __launch_bounds__(64 * WM * WN, (MT * NT >= 16 ? 1 : 2)) void gemm_f16x3_kernel(const GemmP p) {
-  gemm_f16x3_body<MT, NT, WPRE, WM, WN, PF2, AFF, false>(p);
-}
-
-// both operands pre-split (activations produced as fp16 planes by the previous kernel's epilogue, see ops.SplitAct)
-template <int MT, int NT, int WM, int WN, bool PF2>
-__global__ __launch_bounds__(64 * WM * WN, (MT * NT >= 16 ? 1 : 2)) void gemm_f16x3_apre_kernel(const GemmP p) {
-  gemm_f16x3_body<MT, NT, true, WM, WN, PF2, false, true>(p);
+  gemm_f16x3_body<MT, NT, WPRE, WM, WN, PF2, AFF>(p);
 }
 
 // latency-bound launches: PFD K-tiles in flight per workgroup (W pre-split, fp32 A, no fused-BatchNorm operands)
 template <int MT, int NT, int WM, int WN, int PFD>
 __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_f16x3_deep_kernel(const GemmP p) {
-  gemm_f16x3_body<MT, NT, true, WM, WN, true, false, false, PFD>(p);
-}
-
-int gemm_group_m() {
-  static const int v = getenv("PFPP_GEMM_GROUP_M") ? atoi(getenv("PFPP_GEMM_GROUP_M")) : 8;
-  return v;
+  gemm_f16x3_body<MT, NT, true, WM, WN, true, false, PFD>(p);
 }
 
 // =================================================================================================
-// capacity of the caller's split-K workspace for the launch being dispatched (set by pfpp_gemm)
-thread_local int64_t p_split_ws_bytes = 0;
-thread_local int64_t p_split_cnt_len = 0;
+// host side: choose (pure) -> launch (a switch over the choice)
+// =================================================================================================
+// small grids: a 128x128 tiling that cannot fill the 2 x 256 workgroup slots twice over runs as 128x64 tiles; below twice
+// that count the two-deep prefetch kernels run (see choose_kernel)
+constexpr int64_t SMALL_GRID_TILES = 1024;
+// the deep-prefetch kernels take grids of at most this many 64x64 tiles: 3850 x 512 (488 tiles) measured 19.1 us there vs
+// 18.3 us with the 128x64 two-deep kernel
+constexpr int64_t DEEP_MAX_TILES64 = 256;
 
-template <typename K>
-int launch(K kern, size_t smem, GemmP p, int BM, int BN, int batch, hipStream_t st, bool* attr_set, int nthr = 256,
-           bool can_split = false, int min_chunk = 128, bool two_stage_layout = false) {
-  if (!*attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    *attr_set = true;
-  }
-  const int env_group = gemm_group_m();
-  static const int env_pad = getenv("PFPP_GEMM_LDS_PAD") ? atoi(getenv("PFPP_GEMM_LDS_PAD")) : 0;   // experiment knob
+enum class Kern {
+  Planes,               // pre-split A: LDS-DMA staged plane kernel, tile by shape (gemm_pl.hip)
+  PlanesAf32,           // fp32 A read in place by the plane kernel (gemm_pl.hip)
+  Pre256x256,           // register-staged kernels, pre-split W: BM x BN of the tile; Pf2 = two K-tiles in flight,
+  Pre256x128Pf2,        // Aff = fused BatchNorm + ReLU on A as a compile-time property
+  Pre256x128Pf2Aff,
+  Deep64x128,           // latency-bound grids: 4 (GEGLU: value | gate tiles in one wave) or 8 K-tiles in flight
+  Deep64x64,
+  Pre128x64Pf2, Pre128x64, Pre128x128Pf2, Pre128x128,
+  Plain128x128, Plain128x64,                              // fp32 W, split while it is staged
+  F32_128x128, F32_128x64, F32K_128x128, F32K_128x64,     // fp32-MFMA path, W [N,K] / W [K,N]
+};
+
+// The kernel of a validated call: a function of the arguments alone (sizes, flags, which optional pointers are set).
+Kern choose_kernel(const pfpp_gemm_args& a) {
+  // 128-wide tiles unless N is narrow (GEGLU and pool=64 need the 2-tile wave shape)
+  const bool wide = a.N > 64 || a.act == PFPP_ACT_GEGLU;
+  if (a.w_kmajor) return wide ? Kern::F32K_128x128 : Kern::F32K_128x64;
+  if (a.precision == PFPP_GEMM_F32) return wide ? Kern::F32_128x128 : Kern::F32_128x64;
+  // pre-split A (never with the fused-BatchNorm operands: pfpp_gemm rejects the pair): the LDS-DMA staged,
+  // software-pipelined plane kernel
+  if (a.a_hi) return Kern::Planes;
+  if (!a.w_hi) return wide ? Kern::Plain128x128 : Kern::Plain128x64;
+  const bool fused_bn = a.a_mul || a.stats || a.c_min;
+  // big-M GEMMs with a short contraction (the train-mode set-abstraction MLPs: 1.26 M rows, K = 64..256, fused BatchNorm
+  // operand / statistics / pooling): LDS-DMA staged plane kernel with the fp32 A operand converted at fragment-read time
+  if (!a.gather_idx && a.batch == 1 && a.M >= 65536 && a.K % 32 == 0 && a.K <= 256 && a.lda % 4 == 0 &&
+      a.act != PFPP_ACT_GEGLU && !a.c_hi && (a.pool == 0 || a.pool == 32 || a.N > 64))
+    return Kern::PlanesAf32;
+  // 256x128 tile (8 waves): 1.33x more matrix work per byte staged; worth it when there are enough
+  // row panels to fill the chip several times over
+  // operand delivery from L2 is ~11 B/clk/CU whatever the load structure (profiles/README.md), so the
+  // matrix pipe's utilisation is set by bytes per MFMA ~ (BM+BN)/(BM*BN): 256x256 (8 waves of 128x64)
+  // where the grid still fills the chip, 256x128 for narrower N
+  if (wide && a.M >= 8192 && a.N >= 1024 && a.pool == 0 && !a.a_mul) return Kern::Pre256x256;
+  // (two K-tiles in flight on the 256x128 tile too: 16000x512x2048 132 -> 111 us)
+  if (wide && a.M >= 8192 && a.pool != 32) return a.a_mul ? Kern::Pre256x128Pf2Aff : Kern::Pre256x128Pf2;
+  const int64_t tiles128 = ((a.M + 127) / 128) * ((a.N + 127) / 128) * a.batch;
+  // latency-bound launches (see gemm_f16x3_deep_kernel): tiny grids only.
+  // Measured (M = 250: one puzzle's tokens): 512x512 15.9 -> 12.3 us, 1536x512 16.2 -> 12.5, GEGLU 4096x512 24.7 -> 17.8,
+  // 512x2048 (K split into 512-deep chunks instead of 128-deep ones) 40.8 -> 29.7 us; the single-puzzle auto_aggl loop
+  // 4.39 -> 5.28 puzzles/s.  No gain on the wider 3850-row grids.
+  if (!fused_bn && !a.gather_idx && a.pool == 0 && ((a.M + 63) / 64) * ((a.N + 63) / 64) * a.batch <= DEEP_MAX_TILES64)
+    return a.act == PFPP_ACT_GEGLU ? Kern::Deep64x128 : Kern::Deep64x64;
+  // grids of at most ~two workgroups per CU: prefetch two K-tiles ahead (the load latency is all there is to hide);
+  // two-deep prefetch, branch-free steady state: +10..23 % at 3850 rows
+  const bool pf2 = !fused_bn && tiles128 < 2 * SMALL_GRID_TILES;
+  // small grids run as 128x64 tiles (twice the workgroups, same per-wave work shape) — GEGLU / pool=64 need the
+  // 2-tile-wide wave
+  if (wide && tiles128 < SMALL_GRID_TILES && a.act != PFPP_ACT_GEGLU && a.pool == 0) return pf2 ? Kern::Pre128x64Pf2 : Kern::Pre128x64;
+  if (pf2) return wide ? Kern::Pre128x128Pf2 : Kern::Pre128x64Pf2;
+  return wide ? Kern::Pre128x128 : Kern::Pre128x64;
+}
+
+// K chunk of a skinny launch (fewer tiles than CUs, K >= 1024) when the caller lent a workspace: blockIdx.y walks the chunks.
+// Measured on M = 125: 50.6 -> 25.4 us at K = 2048; at K = 512 the fix-up costs more than the four K-tiles it saves, hence
+// the bound.  A chunk holds at least min_chunk / 32 K-tiles.  Returns the chunk length, 0 for no split.
+int choose_k_chunk(const GemmP& p, int64_t tiles, int BM, int BN, int min_chunk, int64_t split_cnt_len) {
+  if (!p.split_ws || !p.split_cnt || tiles >= 192 || p.K < 1024 || p.pool != 0 || p.stats || p.g_idx) return 0;
+  const int want = (int)((384 + tiles - 1) / tiles);
+  const int max_by_k = p.K / min_chunk;
+  int splits = want < max_by_k ? want : max_by_k;
+  if (splits > 16) splits = 16;
+  const int64_t need = (int64_t)splits * tiles * BM * BN * (int64_t)sizeof(float);
+  if (splits <= 1 || need > p.ws_bytes || tiles > split_cnt_len) return 0;
+  const int chunk = (p.K + splits - 1) / splits;
+  return (chunk + 31) / 32 * 32;
+}
+
+// what the entry point knows about a launch beyond the kernel's parameters
+struct Call { int batch; hipStream_t st; int64_t split_cnt_len; };
+
+// min_chunk > 0: the kernel can split K (choose_k_chunk)
+template <auto KERN>
+int launch(size_t smem, GemmP p, int BM, int BN, const Call& c, int nthr = 256, int min_chunk = 0, bool two_stage_layout = false) {
+  (void)pfpp_allow_dyn_lds<KERN>();
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;
-  p.group_m = p.tiles_n > 1 ? env_group : 0;
-  // skinny launches (fewer tiles than CUs, K >= 1024): split K over blockIdx.y when the caller lent a workspace.  Measured on
-  // M = 125: 50.6 -> 25.4 us at K = 2048; at K = 512 the fix-up costs more than the four K-tiles it saves, hence the bound.
-  p.split_k = 1;
-  p.k_chunk = 0;
-  static const bool split_on = !(getenv("PFPP_GEMM_SPLITK") && atoi(getenv("PFPP_GEMM_SPLITK")) == 0);
-  const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n * batch;
-  if (can_split && split_on && p.split_ws && p.split_cnt && tiles < 192 && p.K >= 1024 && p.pool == 0 && !p.stats && !p.g_idx) {
-    int want = (int)((384 + tiles - 1) / tiles);
-    const int max_by_k = p.K / min_chunk;                    // at least min_chunk / 32 K-tiles per chunk (default 4)
-    int splits = want < max_by_k ? want : max_by_k;
-    if (splits > 16) splits = 16;
-    const int64_t need = (int64_t)splits * tiles * BM * BN * (int64_t)sizeof(float);
-    if (splits > 1 && need <= p_split_ws_bytes && tiles <= p_split_cnt_len) {
-      int chunk = (p.K + splits - 1) / splits;
-      chunk = (chunk + 31) / 32 * 32;
-      p.split_k = (p.K + chunk - 1) / chunk;
-      p.k_chunk = chunk;
-    }
-  }
-  const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.split_k, (unsigned)batch);
+  p.group_m = p.tiles_n > 1 ? GROUP_M : 0;
+  p.k_chunk = min_chunk > 0 ? choose_k_chunk(p, (int64_t)p.tiles_m * p.tiles_n * c.batch, BM, BN, min_chunk, c.split_cnt_len) : 0;
+  p.split_k = p.k_chunk ? (p.K + p.k_chunk - 1) / p.k_chunk : 1;
+  const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.split_k, (unsigned)c.batch);
   // a contraction of one K-tile never touches the second LDS stage: allocate one, more workgroups fit a CU (the
   // [1.26 M x 4] first layer of the encoder: 128x64 tiles at 30 KB -> 3 per CU instead of 2, register-limited)
-  static const bool one_stage = !(getenv("PFPP_GEMM_1STAGE") && atoi(getenv("PFPP_GEMM_1STAGE")) == 0);
-  if (two_stage_layout && one_stage && p.K <= 32 && p.split_k == 1) smem /= 2;
-  hipLaunchKernelGGL(kern, grid, dim3(nthr), smem + env_pad, st, p);
+  if (two_stage_layout && p.K <= 32 && p.split_k == 1) smem /= 2;
+  hipLaunchKernelGGL(KERN, grid, dim3(nthr), smem, c.st, p);
   return pfpp::check_launch("pfpp_gemm");
 }
 
+const char* tf(bool b) { return b ? "true" : "false"; }
+
 template <int MT, int NT, bool WK>
-int launch_f32(const GemmP& p, int batch, hipStream_t st) {
+int launch_f32(const GemmP& p, const Call& c) {
   constexpr int BM = 64 * MT, BN = 64 * NT;
   constexpr size_t smem = (size_t)(2 * BM * LDS_LD + 2 * (WK ? BK * BN : BN * LDS_LD)) * sizeof(float);
-  static bool attr_set = false;
-  return launch(gemm_f32_mfma_kernel<MT, NT, WK>, smem, p, BM, BN, batch, st, &attr_set);
+  static const KernelName name("gemm_f32_mfma_kernel<%d, %d, %s>", MT, NT, tf(WK));
+  report_kernel(name);
+  return launch<gemm_f32_mfma_kernel<MT, NT, WK>>(smem, p, BM, BN, c);
 }
 
 template <int MT, int NT, bool WPRE, int WM = 2, int WN = 2, bool PF2 = false, bool AFF = false>
-int launch_f16x3(const GemmP& p, int batch, hipStream_t st) {
+int launch_f16x3(const GemmP& p, const Call& c) {
   constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
   constexpr size_t smem = (size_t)2 * (2 * BM * LDH + 2 * BN * LDH) * sizeof(_Float16);
-  static bool attr_set = false;
-  return launch(gemm_f16x3_kernel<MT, NT, WPRE, WM, WN, PF2, AFF>, smem, p, BM, BN, batch, st, &attr_set, 64 * WM * WN, true, 128, true);
+  static const KernelName name("gemm_f16x3_kernel<%d, %d, %s, %d, %d, %s, %s>", MT, NT, tf(WPRE), WM, WN, tf(PF2), tf(AFF));
+  report_kernel(name);
+  return launch<gemm_f16x3_kernel<MT, NT, WPRE, WM, WN, PF2, AFF>>(smem, p, BM, BN, c, 64 * WM * WN, 128, true);
 }
 
 template <int MT, int NT, int WM, int WN, int PFD>
-int launch_f16x3_deep(const GemmP& p, int batch, hipStream_t st) {
+int launch_f16x3_deep(const GemmP& p, const Call& c) {
   constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
   constexpr size_t smem = (size_t)2 * (2 * BM * LDH + 2 * BN * LDH) * sizeof(_Float16);
-  static bool attr_set = false;
+  static const KernelName name("gemm_f16x3_deep_kernel<%d, %d, %d, %d, %d>", MT, NT, WM, WN, PFD);
+  report_kernel(name);
   // split K only into chunks that still fill the prefetch pipeline twice over (the fix-up reads one partial per chunk)
-  return launch(gemm_f16x3_deep_kernel<MT, NT, WM, WN, PFD>, smem, p, BM, BN, batch, st, &attr_set, 64 * WM * WN, true, 512);
-}
-
-template <int MT, int NT, int WM, int WN, bool PF2>
-int launch_f16x3_apre(const GemmP& p, int batch, hipStream_t st) {
-  constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
-  constexpr size_t smem = (size_t)2 * (2 * BM * LDH + 2 * BN * LDH) * sizeof(_Float16);
-  static bool attr_set = false;
-  return launch(gemm_f16x3_apre_kernel<MT, NT, WM, WN, PF2>, smem, p, BM, BN, batch, st, &attr_set, 64 * WM * WN, true);
+  return launch<gemm_f16x3_deep_kernel<MT, NT, WM, WN, PFD>>(smem, p, BM, BN, c, 64 * WM * WN, 512);
 }
 
 }  // namespace
 
-namespace pfpp_gemm_detail { namespace pl { extern thread_local char last_kernel[96]; } }
-
 extern "C" int pfpp_gemm(const pfpp_gemm_args* a, pfpp_stream_t stream) {
-  pfpp_gemm_detail::pl::last_kernel[0] = 0;
+  pl::last_kernel[0] = 0;      // a call that launches nothing (M == 0, rejected arguments) reports ""
   PFPP_REQUIRE(a && (a->A || (a->a_hi && a->a_lo) || (a->gather_idx && a->lda == 0)) && (a->C || (a->c_hi && a->c_lo)), "null pointer");
   PFPP_REQUIRE(a->W || (a->w_hi && a->w_lo), "W (or its pre-split planes) missing");
   PFPP_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0, "bad sizes");
@@ -915,93 +849,32 @@ extern "C" int pfpp_gemm(const pfpp_gemm_args* a, pfpp_stream_t stream) {
   p.split_ws = a->split_ws; p.split_cnt = a->split_cnt; p.split_k = 1; p.k_chunk = 0;
   p.g_idx = a->gather_idx; p.g_xyz = a->gather_xyz; p.g_ctr = a->gather_ctr;
   p.g_N = a->gather_N; p.g_S = a->gather_S; p.g_ns = a->gather_ns;
-  p_split_ws_bytes = a->split_ws ? a->split_ws_bytes : 0;
-  p.ws_bytes = p_split_ws_bytes;
-  p_split_cnt_len = a->split_cnt ? a->split_cnt_len : 0;
+  p.ws_bytes = a->split_ws ? a->split_ws_bytes : 0;
   p.tiles_n = 0;
-  p.dbg = 0;
   p.accum = 0;
   p.x1 = a->precision == PFPP_GEMM_F16 ? 1 : 0;
   p.k_valid = (int)a->K;
   hipStream_t st = pfpp::as_stream(stream);
 
-  // 128x128 tiles unless N is narrow (GEGLU and pool=64 need the 2-tile wave shape)
-  const bool wide = a->N > 64 || a->act == PFPP_ACT_GEGLU;
-  if ((a->precision == PFPP_GEMM_F16X3 || a->precision == PFPP_GEMM_F16) && !a->w_kmajor) {
-    // LDS-DMA staged, software-pipelined plane kernel (gemm_pl.hip).  PFPP_GEMM_PL: 0 = off, 1..3 = force a tile, unset / -1 = by shape
-    if (apre && !fused_bn && true) {
-      const char* e = getenv("PFPP_GEMM_PL");
-      const int v = e ? atoi(e) : -1;
-      if (v != 0) return launch_f16x3_planes(p, a->batch, st, gemm_group_m(), v < 0 ? 0 : v);
-    }
-    if (apre) {
-      // the register-staged kernels with A staged like W (no conversions in the loop); same tile choice as below
-      static const bool big = !(getenv("PFPP_GEMM_BIG") && atoi(getenv("PFPP_GEMM_BIG")) == 0);
-      if (big && a->M >= 8192 && a->N >= 1024 && a->pool == 0) return launch_f16x3_apre<4, 2, 2, 4, false>(p, a->batch, st);
-      if (big && a->M >= 8192 && a->pool != 32) return launch_f16x3_apre<2, 2, 4, 2, true>(p, a->batch, st);
-      const int64_t t128 = ((a->M + 127) / 128) * ((a->N + 127) / 128) * a->batch;
-      if (t128 < 1024 && a->act != PFPP_ACT_GEGLU && a->pool == 0) return launch_f16x3_apre<2, 1, 2, 2, true>(p, a->batch, st);
-      return launch_f16x3_apre<2, 2, 2, 2, true>(p, a->batch, st);
-    }
-    // big-M GEMMs with a short contraction (the train-mode set-abstraction MLPs: 1.26 M rows, K = 64..256, fused BatchNorm
-    // operand / statistics / pooling): LDS-DMA staged plane kernel with the fp32 A operand converted at fragment-read time
-    static const bool af32 = !(getenv("PFPP_GEMM_AF32") && atoi(getenv("PFPP_GEMM_AF32")) == 0);
-    if (af32 && pre && !apre && !a->gather_idx && a->batch == 1 && a->M >= 65536 && a->K % 32 == 0 && a->K <= 256 && a->lda % 4 == 0 &&
-        a->act != PFPP_ACT_GEGLU && !a->c_hi && (a->pool == 0 || a->pool == 32 || a->N > 64))
-      return launch_f16x3_planes_af32(p, a->batch, st, gemm_group_m());
-    static const bool big_tile = !(getenv("PFPP_GEMM_BIG") && atoi(getenv("PFPP_GEMM_BIG")) == 0);
-    // 256x128 tile (8 waves): 1.33x more matrix work per byte staged; worth it when there are enough
-    // row panels to fill the chip several times over
-    // operand delivery from L2 is ~11 B/clk/CU whatever the load structure (profiles/README.md), so the
-    // matrix pipe's utilisation is set by bytes per MFMA ~ (BM+BN)/(BM*BN): 256x256 (8 waves of 128x64)
-    // where the grid still fills the chip, 256x128 for narrower N
-    if (pre && wide && big_tile && a->M >= 8192 && a->N >= 1024 && a->pool == 0 && !a->a_mul)
-      return launch_f16x3<4, 2, true, 2, 4>(p, a->batch, st);
-    // train-mode encoder GEMMs (fused BatchNorm operands) run on their own stream UNDER the transformer's latency-bound
-    // kernels: a tile whose LDS footprint leaves room for a second workgroup lets those co-reside (160 KB per CU:
-    // 256x128 = 120 KB blocks a 61 KB transformer tile, 128x128 = 80 KB does not)
-    static const int bn_tile = getenv("PFPP_GEMM_BN_TILE") ? atoi(getenv("PFPP_GEMM_BN_TILE")) : 0;
-    if (pre && wide && fused_bn && bn_tile > 0 && a->M >= 8192) {
-      if (bn_tile == 3) return launch_f16x3<2, 2, true>(p, a->batch, st);     // one K-tile in flight, more workgroups per CU
-      if (bn_tile == 2 && a->pool == 0)
-        return a->a_mul ? launch_f16x3<2, 1, true, 2, 2, true, true>(p, a->batch, st) : launch_f16x3<2, 1, true, 2, 2, true>(p, a->batch, st);
-      return a->a_mul ? launch_f16x3<2, 2, true, 2, 2, true, true>(p, a->batch, st) : launch_f16x3<2, 2, true, 2, 2, true>(p, a->batch, st);
-    }
-    static const bool pf2_big = !(getenv("PFPP_GEMM_PF2BIG") && atoi(getenv("PFPP_GEMM_PF2BIG")) == 0);   // 16000x512x2048: 132 -> 111 us
-    if (pre && wide && big_tile && a->M >= 8192 && a->pool != 32)
-      return !pf2_big ? launch_f16x3<2, 2, true, 4, 2>(p, a->batch, st)
-             : a->a_mul ? launch_f16x3<2, 2, true, 4, 2, true, true>(p, a->batch, st)
-                        : launch_f16x3<2, 2, true, 4, 2, true>(p, a->batch, st);
-    // small grids: a 128x128 tiling that cannot fill the 2 x 256 workgroup slots twice over runs as 128x64
-    // tiles (twice the workgroups, same per-wave work shape) — GEGLU / pool=64 need the 2-tile-wide wave
-    static const int small_thresh = getenv("PFPP_GEMM_SMALL") ? atoi(getenv("PFPP_GEMM_SMALL")) : 1024;
-    const int64_t tiles128 = ((a->M + 127) / 128) * ((a->N + 127) / 128) * a->batch;
-    // grids of at most ~two workgroups per CU: prefetch two K-tiles ahead (the load latency is all there is to hide)
-    // latency-bound launches (see gemm_f16x3_deep_kernel).  PFPP_GEMM_DEEP: 0 off, 1 tiny grids only, 2 also the 3850-row grids
-    // Measured (M = 250: one puzzle's tokens): 512x512 15.9 -> 12.3 us, 1536x512 16.2 -> 12.5, GEGLU 4096x512 24.7 -> 17.8,
-    // 512x2048 (K split into 512-deep chunks instead of 128-deep ones) 40.8 -> 29.7 us; the single-puzzle auto_aggl loop
-    // 4.39 -> 5.28 puzzles/s.  No gain on the wider 3850-row grids (PFPP_GEMM_DEEP=2 routes them here too).  0 = off.
-    static const int deep_mode = getenv("PFPP_GEMM_DEEP") ? atoi(getenv("PFPP_GEMM_DEEP")) : 1;
-    if (pre && deep_mode > 0 && !fused_bn && !a->gather_idx && a->pool == 0) {
-      const int64_t t64 = ((a->M + 63) / 64) * ((a->N + 63) / 64) * a->batch;
-      if (t64 <= 256) {      // 3850 x 512 (488 tiles) measured 19.1 us here vs 18.3 us with the 128x64 two-deep kernel
-        if (a->act == PFPP_ACT_GEGLU) return launch_f16x3_deep<1, 2, 2, 2, 4>(p, a->batch, st);
-        return launch_f16x3_deep<1, 1, 2, 2, 8>(p, a->batch, st);
-      }
-      if (deep_mode > 1 && wide && tiles128 < small_thresh && a->act != PFPP_ACT_GEGLU)
-        return launch_f16x3_deep<2, 1, 2, 2, 4>(p, a->batch, st);
-    }
-    static const bool pf2 = !(getenv("PFPP_GEMM_PF2") && atoi(getenv("PFPP_GEMM_PF2")) == 0);   // two-deep prefetch, branch-free steady state: +10..23 % at 3850 rows
-    const bool deep = pf2 && !fused_bn && tiles128 < 2 * small_thresh;
-    if (pre && wide && tiles128 < small_thresh && a->act != PFPP_ACT_GEGLU && a->pool == 0)
-      return deep ? launch_f16x3<2, 1, true, 2, 2, true>(p, a->batch, st) : launch_f16x3<2, 1, true>(p, a->batch, st);
-    if (pre && deep)
-      return wide ? launch_f16x3<2, 2, true, 2, 2, true>(p, a->batch, st) : launch_f16x3<2, 1, true, 2, 2, true>(p, a->batch, st);
-    if (pre) return wide ? launch_f16x3<2, 2, true>(p, a->batch, st) : launch_f16x3<2, 1, true>(p, a->batch, st);
-    return wide ? launch_f16x3<2, 2, false>(p, a->batch, st) : launch_f16x3<2, 1, false>(p, a->batch, st);
+  const Call c{(int)a->batch, st, a->split_cnt ? a->split_cnt_len : 0};
+  switch (choose_kernel(*a)) {
+    case Kern::Planes: return launch_f16x3_planes(p, c.batch, st);
+    case Kern::PlanesAf32: return launch_f16x3_planes_af32(p, c.batch, st);
+    case Kern::Pre256x256: return launch_f16x3<4, 2, true, 2, 4>(p, c);
+    case Kern::Pre256x128Pf2: return launch_f16x3<2, 2, true, 4, 2, true>(p, c);
+    case Kern::Pre256x128Pf2Aff: return launch_f16x3<2, 2, true, 4, 2, true, true>(p, c);
+    case Kern::Deep64x128: return launch_f16x3_deep<1, 2, 2, 2, 4>(p, c);
+    case Kern::Deep64x64: return launch_f16x3_deep<1, 1, 2, 2, 8>(p, c);
+    case Kern::Pre128x64Pf2: return launch_f16x3<2, 1, true, 2, 2, true>(p, c);
+    case Kern::Pre128x64: return launch_f16x3<2, 1, true>(p, c);
+    case Kern::Pre128x128Pf2: return launch_f16x3<2, 2, true, 2, 2, true>(p, c);
+    case Kern::Pre128x128: return launch_f16x3<2, 2, true>(p, c);
+    case Kern::Plain128x128: return launch_f16x3<2, 2, false>(p, c);
+    case Kern::Plain128x64: return launch_f16x3<2, 1, false>(p, c);
+    case Kern::F32_128x128: return launch_f32<2, 2, false>(p, c);
+    case Kern::F32_128x64: return launch_f32<2, 1, false>(p, c);
+    case Kern::F32K_128x128: return launch_f32<2, 2, true>(p, c);
+    case Kern::F32K_128x64: return launch_f32<2, 1, true>(p, c);
   }
-  if (a->w_kmajor) {
-    return wide ? launch_f32<2, 2, true>(p, a->batch, st) : launch_f32<2, 1, true>(p, a->batch, st);
-  }
-  return wide ? launch_f32<2, 2, false>(p, a->batch, st) : launch_f32<2, 1, false>(p, a->batch, st);
+  return PFPP_EINVAL;      // (not reached: the switch covers the enumeration)
 }

@@ -3,6 +3,9 @@
 // residual / max over row groups).  Accumulator layout of a 32x32 MFMA tile (dtype independent on
 // gfx950): element e of lane l is C[row = (e&3) + 8*(e>>2) + 4*(l>>5)][col = l&31].
 #pragma once
+#include <stdarg.h>
+#include <string.h>
+
 #include "pfpp_common.h"
 
 namespace pfpp_gemm_detail {
@@ -39,8 +42,24 @@ struct GemmP {
   float* csum; float* csum_ws; float csum_alpha;   // gemm_pl.hip (k-major A): csum[m] += csum_alpha * sum_k A[k][m] — the bias gradient riding in dW = dY^T . X
   int accum;  // gemm_pl.hip: C += alpha * acc with fp32 atomics (set by the launcher for split-K / gradient accumulation)
   pfpp_slab_job* defer;   // host side only (gemm_pl.hip launch_pl): hand the slab reduction back instead of launching it
-  int dbg;    // gemm_pl.hip ablation switches (PFPP_GEMM_DBG; developer runs only): 1 no epilogue, 2 no DMA after the prologue, 4 no barrier / DMA wait
+  int reserved;   // always 0 (once a mask of lab ablation switches): kept so that the layout, and with it every kernel's argument offsets, stays as it was
 };
+
+// template instantiation (and "+pl_reduce_kernel" where a slab reduction follows) of the most recent GEMM launch of this
+// thread: written by every launcher of gemm.hip, gemm_pl.hip and gemm_grad.hip, read by pfpp_last_gemm_kernel (gemm_pl.hip)
+namespace pl { extern thread_local char last_kernel[96]; }
+// A launcher formats the name of its instantiation once (a function-local static) and copies it per launch: no printf on the
+// launch path.  80 characters + the longest suffix (17) fit last_kernel.
+struct KernelName {
+  char s[80];
+  explicit KernelName(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(s, sizeof(s), fmt, ap);
+    va_end(ap);
+  }
+};
+inline void report_kernel(const KernelName& name, const char* suffix = "") { strcpy(stpcpy(pl::last_kernel, name.s), suffix); }
 
 __device__ __forceinline__ float act_apply(float v, int act) {
   switch (act) {
@@ -62,6 +81,7 @@ __device__ __forceinline__ int remap_tile(int bid, int nwg) {
 // tile id -> (tm, tn).  group_m > 0: ids walk group_m consecutive row panels column by column, so
 // the ~64 tiles an XCD runs at once span group_m panels of A and 64/group_m panels of W (L2 reuse of
 // both operands); group_m == 0: plain row-major order.
+constexpr int GROUP_M = 8;     // what every launcher passes when there is more than one tile column
 __device__ __forceinline__ void tile_coords(const GemmP& p, int tile, int& tm, int& tn) {
   if (p.group_m > 0) {
     const int group = p.group_m * p.tiles_n;

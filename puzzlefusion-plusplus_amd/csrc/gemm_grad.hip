@@ -15,8 +15,6 @@
 // Weight gradients have few output tiles and a long contraction (all tokens): the K range is cut into
 // `split_k` chunks over blockIdx.y which accumulate with hardware fp32 atomics (`accumulate`, also
 // what lets several micro-batches add into one .grad buffer).
-#include <stdlib.h>
-
 #include "gemm_common.h"
 
 namespace {
@@ -390,66 +388,88 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_grad_group_kernel(const 
   grad_tile<MT, NT, WM, WN, AKM, WKM>(p, tile, ksplit, 0);
 }
 
+// ---- host side: choose (pure) -> launch --------------------------------------------------------------------------------------
+// auto split of a weight gradient: ~this many workgroups, chunks at least GRAD_MIN_CHUNK deep.  Measured on the [3850-token]
+// training step after the K loop became one scheduling region (each workgroup is faster, so fewer, deeper chunks win — less
+// atomic traffic): (384, 512) 8.66 ms, (256, 512) 8.48, (192, 512) 8.29, (256, 1024) 8.28, (320, 1024) 8.33, (256, 2048) 8.93 per
+// iteration; again with the chunk-major XCD assignment: (256, 1024) 8.27, (256, 768) 8.19, (224, 768) 8.28, (192, 896) 8.22,
+// (192, 768) 8.16, (192, 640) 8.15, (160, 768) 8.20, (128, 1024) 8.83
+constexpr int GRAD_TARGET_WG = 192;
+constexpr int GRAD_MIN_CHUNK = 768;
+// accumulating [512x512]-sized outputs (fewer 128x128 tiles than this): 128x64 tiles (45 -> 40.6 us)
+constexpr int GRAD_SMALL_TILES = 40;
+// the grouped launch: one K split factor for the whole group — enough workgroups for ~2 per CU (with the group's tiles)
+constexpr int GRAD_GROUP_TARGET_WG = 1024;
+constexpr int GRAD_GROUP_MIN_CHUNK = 640;
+
+enum class GradTile { T256x128, T128x128, T128x64 };
+struct GradChoice { GradTile tile; int splits; int k_chunk; };
+
+// K range per chunk (a multiple of BK) for `want` chunks, and how many chunks that makes
+void chunk_k(int K, int64_t want, int* splits, int* k_chunk) {
+  int chunk = (int)((K + want - 1) / want);
+  chunk = (chunk + BK - 1) / BK * BK;
+  *splits = (K + chunk - 1) / chunk;
+  *k_chunk = chunk;
+}
+
+// tile shape by how many workgroups the output gives (256x128 when that still fills the chip), then the K split;
+// split_k <= 0: automatic
+GradChoice choose_grad(int M, int N, int K, int batch, bool accumulate, int split_k) {
+  const auto tiles = [&](int bm, int bn) { return (int64_t)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * batch; };
+  int bm = 128, bn = 64;
+  if (tiles(256, 128) >= 384) { bm = 256; bn = 128; }
+  else if (tiles(128, 128) >= 256 || N > 64) { bm = 128; bn = 128; }
+  if (bm == 128 && bn == 128 && tiles(128, 128) < 192 && split_k == 1 && N <= 2048) { bn = 64; }
+  if (bm == 128 && bn == 128 && accumulate && tiles(128, 128) < GRAD_SMALL_TILES) { bn = 64; }
+  int64_t want = split_k;
+  if (want <= 0 && !accumulate) want = 1;     // a plain store cannot be split
+  if (want <= 0) {
+    const int64_t t = tiles(bm, bn);
+    want = (GRAD_TARGET_WG + t - 1) / t;
+    const int64_t max_by_k = (K + GRAD_MIN_CHUNK - 1) / GRAD_MIN_CHUNK;
+    if (want > max_by_k) want = max_by_k;
+    if (want < 1) want = 1;
+  }
+  GradChoice c;
+  c.tile = bm == 256 ? GradTile::T256x128 : (bn == 128 ? GradTile::T128x128 : GradTile::T128x64);
+  chunk_k(K, want, &c.splits, &c.k_chunk);
+  return c;
+}
+
 template <int MT, int NT, int WM, int WN, bool AKM, bool WKM>
-int launch_grad(GradP p, int batch, int splits, hipStream_t st) {
+int launch_grad(GradP p, int batch, const GradChoice& c, hipStream_t st) {
   constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
   constexpr size_t smem = (size_t)2 * (2 * BM * LDH + 2 * BN * LDH) * sizeof(_Float16);
-  static bool attr_set = false;
-  auto kern = gemm_grad_kernel<MT, NT, WM, WN, AKM, WKM>;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = gemm_grad_kernel<MT, NT, WM, WN, AKM, WKM>;
+  (void)pfpp_allow_dyn_lds<kern>();
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;
-  p.group_m = p.tiles_n > 1 ? 8 : 0;
-  // chunk-major XCD assignment of split-K launches (training iteration 8.52 -> 8.36 ms, one stream 11.59 -> 11.36); 0 = tile-major
-  static const bool kxcd = !(getenv("PFPP_GRAD_KXCD") && atoi(getenv("PFPP_GRAD_KXCD")) == 0);
-  p.kxcd = kxcd && splits > 1;
-  const dim3 grid = p.kxcd ? dim3((unsigned)(p.tiles_m * p.tiles_n * splits), 1u, (unsigned)batch)
-                           : dim3((unsigned)(p.tiles_m * p.tiles_n), (unsigned)splits, (unsigned)batch);
+  p.group_m = p.tiles_n > 1 ? GROUP_M : 0;
+  p.k_chunk = c.k_chunk;
+  // split-K launches are chunk-major over the XCDs (see gemm_grad_kernel): training iteration 8.52 -> 8.36 ms, one stream 11.59 -> 11.36
+  p.kxcd = c.splits > 1;
+  const dim3 grid = p.kxcd ? dim3((unsigned)(p.tiles_m * p.tiles_n * c.splits), 1u, (unsigned)batch)
+                           : dim3((unsigned)(p.tiles_m * p.tiles_n), (unsigned)c.splits, (unsigned)batch);
+  static const KernelName name("gemm_grad_kernel<%d, %d, %d, %d, %s, %s>", MT, NT, WM, WN, AKM ? "true" : "false", WKM ? "true" : "false");
+  report_kernel(name);
   hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), smem, st, p);
   return pfpp::check_launch("pfpp_gemm_grad");
 }
 
 template <bool AKM, bool WKM>
-int dispatch(GradP p, int batch, int split_k, hipStream_t st) {
-  // tile shape by how many workgroups the output gives: 256x128 when that still fills the chip
-  const auto tiles = [&](int bm, int bn) { return (int64_t)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * batch; };
-  int bm = 128, bn = 64;
-  static const bool big_split = getenv("PFPP_GRAD_BIG") && atoi(getenv("PFPP_GRAD_BIG")) == 1;   // experiment knob
-  if (tiles(256, 128) >= 384 || (big_split && p.accumulate && split_k != 1 && p.M >= 256 && p.N >= 128)) { bm = 256; bn = 128; }
-  else if (tiles(128, 128) >= 256 || p.N > 64) { bm = 128; bn = 128; }
-  if (bm == 128 && bn == 128 && tiles(128, 128) < 192 && split_k == 1 && p.N <= 2048) { bn = 64; }
-  static const int small_tiles = getenv("PFPP_GRAD_SMALL") ? atoi(getenv("PFPP_GRAD_SMALL")) : 40;   // [512x512]-sized outputs: 128x64 tiles (45 -> 40.6 us)
-  if (bm == 128 && bn == 128 && p.accumulate && tiles(128, 128) < small_tiles) { bn = 64; }
-  int splits = split_k;
-  if (splits <= 0 && !p.accumulate) splits = 1;     // a plain store cannot be split
-  if (splits <= 0) {
-    // auto: ~1 workgroup per CU, chunks at least 1024 deep.  Measured on the [3850-token] training step after the K loop
-    // became one scheduling region (each workgroup is faster, so fewer, deeper chunks win — less atomic traffic):
-    // (384, 512) 8.66 ms, (256, 512) 8.48, (192, 512) 8.29, (256, 1024) 8.28, (320, 1024) 8.33, (256, 2048) 8.93 per iteration;
-    // again with the chunk-major XCD assignment: (256, 1024) 8.27, (256, 768) 8.19, (224, 768) 8.28, (192, 896) 8.22,
-    // (192, 768) 8.16, (192, 640) 8.15, (160, 768) 8.20, (128, 1024) 8.83
-    static const int target_wg = getenv("PFPP_GRAD_WG") ? atoi(getenv("PFPP_GRAD_WG")) : 192;
-    static const int min_k = getenv("PFPP_GRAD_MINK") ? atoi(getenv("PFPP_GRAD_MINK")) : 768;
-    const int64_t t = tiles(bm, bn);
-    int64_t want = (target_wg + t - 1) / t;
-    const int64_t max_by_k = (p.K + min_k - 1) / min_k;
-    if (want > max_by_k) want = max_by_k;
-    splits = (int)(want < 1 ? 1 : want);
-  }
-  int chunk = (p.K + splits - 1) / splits;
-  chunk = (chunk + BK - 1) / BK * BK;
-  splits = (p.K + chunk - 1) / chunk;
-  p.k_chunk = chunk;
-  if (splits > 1 && !p.accumulate) {
+int dispatch(const GradP& p, int batch, int split_k, hipStream_t st) {
+  const GradChoice c = choose_grad(p.M, p.N, p.K, batch, p.accumulate != 0, split_k);
+  if (c.splits > 1 && !p.accumulate) {
     pfpp::set_error("pfpp_gemm_grad: split_k > 1 needs accumulate (zero-initialised output)");
     return PFPP_EINVAL;
   }
-  if (bm == 256) return launch_grad<2, 2, 4, 2, AKM, WKM>(p, batch, splits, st);
-  if (bn == 128) return launch_grad<2, 2, 2, 2, AKM, WKM>(p, batch, splits, st);
-  return launch_grad<2, 1, 2, 2, AKM, WKM>(p, batch, splits, st);
+  switch (c.tile) {
+    case GradTile::T256x128: return launch_grad<2, 2, 4, 2, AKM, WKM>(p, batch, c, st);
+    case GradTile::T128x128: return launch_grad<2, 2, 2, 2, AKM, WKM>(p, batch, c, st);
+    case GradTile::T128x64: return launch_grad<2, 1, 2, 2, AKM, WKM>(p, batch, c, st);
+  }
+  return PFPP_EINVAL;      // (not reached)
 }
 
 }  // namespace
@@ -523,24 +543,18 @@ extern "C" int pfpp_gemm_grad_group(const pfpp_gemm_grad_args* args, int count, 
     GradP& p = g.p[i];
     p.tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = (p.N + BN - 1) / BN;
-    p.group_m = p.tiles_n > 1 ? 8 : 0;
+    p.group_m = p.tiles_n > 1 ? GROUP_M : 0;
     tiles_total += (int64_t)p.tiles_m * p.tiles_n;
   }
-  // one K split factor for the whole group: enough workgroups for ~2 per CU, chunks at least `min_k` deep
-  static const int target_wg = getenv("PFPP_GRAD_GROUP_WG") ? atoi(getenv("PFPP_GRAD_GROUP_WG")) : 1024;
-  static const int min_k = getenv("PFPP_GRAD_GROUP_MINK") ? atoi(getenv("PFPP_GRAD_GROUP_MINK")) : 640;
   int start = 0;
   for (int i = 0; i < count; ++i) {
     GradP& p = g.p[i];
-    int64_t want = (target_wg + tiles_total / 2) / tiles_total;
-    const int64_t max_by_k = (p.K + min_k - 1) / min_k;
+    int64_t want = (GRAD_GROUP_TARGET_WG + tiles_total / 2) / tiles_total;
+    const int64_t max_by_k = (p.K + GRAD_GROUP_MIN_CHUNK - 1) / GRAD_GROUP_MIN_CHUNK;
     if (want > max_by_k) want = max_by_k;
     if (want < 1 || !p.accumulate) want = 1;              // a plain store cannot be split
     if (args[i].split_k > 0) want = args[i].split_k;
-    int chunk = (int)((p.K + want - 1) / want);
-    chunk = (chunk + BK - 1) / BK * BK;
-    p.splits = (p.K + chunk - 1) / chunk;
-    p.k_chunk = chunk;
+    chunk_k(p.K, want, &p.splits, &p.k_chunk);
     PFPP_REQUIRE(p.splits == 1 || p.accumulate, "split_k > 1 needs accumulate (zero-initialised output)");
     p.atomic = p.splits > 1;
     g.wg_start[i] = start;
@@ -549,12 +563,10 @@ extern "C" int pfpp_gemm_grad_group(const pfpp_gemm_grad_args* args, int count, 
   for (int i = count; i <= MAX_GROUP; ++i) g.wg_start[i] = start;
   g.count = count;
   constexpr size_t smem = (size_t)2 * (2 * BM * LDH + 2 * BN * LDH) * sizeof(_Float16);
-  auto kern = gemm_grad_group_kernel<2, 2, 2, 2, true, true>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = gemm_grad_group_kernel<2, 2, 2, 2, true, true>;
+  (void)pfpp_allow_dyn_lds<kern>();
+  static const KernelName name("gemm_grad_group_kernel<2, 2, 2, 2, true, true>");
+  report_kernel(name);
   hipLaunchKernelGGL(kern, dim3((unsigned)start), dim3(256), smem, pfpp::as_stream(stream), g);
   return pfpp::check_launch("pfpp_gemm_grad_group");
 }

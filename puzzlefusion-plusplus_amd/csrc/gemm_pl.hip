@@ -29,19 +29,15 @@
 // Fragment reads are inline asm (hipcc drains vmcnt(0) in front of every ds_read it can see while an LDS-DMA is
 // in flight); the waits name every destination register, which is what orders the MFMAs behind them.
 // One __shared__ object only (a second one makes hipcc drain the DMA queue at every step, guide §5).
-#include <stdlib.h>
+#include <math.h>
 #include <string.h>
 
-#include <type_traits>
-#include <utility>
-
 #include "gemm_common.h"
+#include "lds_asm.h"
 
 namespace pfpp_gemm_detail {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
+using namespace pfpp_lds;
 
 namespace pl {
 
@@ -50,34 +46,10 @@ namespace pl {
 __device__ __attribute__((aligned(64))) char pl_zero_row[64] = {0};
 
 constexpr int BK = 32;
-thread_local int64_t p_ws_bytes = 0;     // capacity of the caller's K-split workspace for the launch being dispatched
-thread_local char last_kernel[96] = "";  // template instantiation of the most recent plane-GEMM launch of this thread (pfpp_last_gemm_kernel)
+thread_local char last_kernel[96] = "";  // see gemm_common.h
 
 __device__ __forceinline__ void glds16(const char* gsrc, uint32_t ldst) {
   __builtin_amdgcn_global_load_lds((gbl_void*)gsrc, (lds_void*)(uintptr_t)ldst, 16, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt immediate");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int OFF>
-__device__ __forceinline__ half8 lds_rd(uint32_t addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
-  half8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
 // MT x NT 32x32 tiles per wave, WM x WN waves.  HS = row tiles per half-step (the fragment double buffer holds HS row tiles
@@ -240,7 +212,7 @@ __device__ __forceinline__ void epilogue_wide(const GemmP& p, f32x16 (&acc)[MT][
 // One workgroup = one output tile.  NS-stage DMA ring; see the header for the schedule.
 // EXT: the (tile, K chunk) of this workgroup comes from the caller (ext_tile of the problem's row-major tile list, whole contraction)
 // instead of blockIdx — the grouped weight-gradient launch, where a workgroup first finds its problem in a table.
-template <int MT, int NT, int WM, int WN, int NS, bool AK, bool WK, int DBG, bool AF = false, bool X1 = false, bool CS = false, bool EXT = false>
+template <int MT, int NT, int WM, int WN, int NS, bool AK, bool WK, bool AF = false, bool X1 = false, bool CS = false, bool EXT = false>
 __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
   static_assert(!(AF && AK), "an fp32 A operand is row-major");
   static_assert(!CS || (AK && !X1), "column sums ride with a k-major split A operand (dW = dY^T . X)");
@@ -414,15 +386,11 @@ __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
   struct FB { half8 h[NT], l[NT]; half4 h2[WK ? NT : 1][2], l2[WK ? NT : 1][2]; };
   FA fa[2];
   FB fb[2];
-  // DBG (lab builds, -DPFPP_PL_LAB): 1 no epilogue, 2 no DMA after the prologue, 4 no barrier / DMA wait, 8 no fragment reads,
-  // 16 no fragment waits
-  constexpr bool dbg_noread = DBG & 8, dbg_nowait = DBG & 16;
   // Fragment reads one at a time, each in its own gap between two MFMAs.  Row-major: q < HS: hi plane of row tile q, then
   // the lo planes.  K-major: q = 4 * tile + 2 * plane + t.
   int kt_aff = 0;          // AF: K-tile the next fragment reads belong to (selects the slice of the affine table)
   auto rd_a = [&](FA& f, uint32_t st, auto s_c, auto mh_c, auto q_c) {
     constexpr int s = decltype(s_c)::value, mh = decltype(mh_c)::value, q = decltype(q_c)::value;
-    if constexpr (dbg_noread) return;
     if constexpr (AK) {
       constexpr int t = q / (2 * NPL), pl_ = (q >> 1) % NPL, hf = q & 1;
       constexpr int off = pl_ * C::PLANE_A + (16 * s + 4 * hf) * CPR_A * 16;
@@ -446,7 +414,6 @@ __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
   };
   auto rd_b = [&](FB& f, uint32_t st, auto s_c, auto q_c) {
     constexpr int s = decltype(s_c)::value, q = decltype(q_c)::value;
-    if constexpr (dbg_noread) return;
     if constexpr (WK) {
       constexpr int t = q / (2 * NPL), pl_ = (q >> 1) % NPL, hf = q & 1;
       constexpr int off = pl_ * C::PLANE_W + (16 * s + 4 * hf) * CPR_W * 16;
@@ -462,7 +429,6 @@ __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
   // all outstanding LDS reads have landed; names the fragments the following MFMAs consume (k-major: and joins their halves)
   auto join = [](const half4 x, const half4 y) { return __builtin_shufflevector(x, y, 0, 1, 2, 3, 4, 5, 6, 7); };
   auto wait_a = [&](FA& a) {
-    if constexpr (dbg_nowait) return;
     if constexpr (X1 && AK) {
       static_for<HS>([&](auto t_c) {
         constexpr int t = decltype(t_c)::value;
@@ -503,7 +469,6 @@ __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
                    : "+v"(a.h[0]), "+v"(a.h[1]), "+v"(a.h[2]), "+v"(a.h[3]), "+v"(a.l[0]), "+v"(a.l[1]), "+v"(a.l[2]), "+v"(a.l[3]));
   };
   auto wait_b = [&](FB& b) {
-    if constexpr (dbg_nowait) return;
     if constexpr (X1 && WK) {
       static_for<NT>([&](auto t_c) {
         constexpr int t = decltype(t_c)::value;
@@ -605,17 +570,15 @@ __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
   auto tile_body = [&](int kt, uint32_t cur, uint32_t nxt, uint32_t prv, auto last_c) {
     constexpr bool LAST = decltype(last_c)::value;
     kt_aff = kt;
-    const bool dma2 = !(DBG & 2) && kt >= 1 && kt + NS - 1 < nk;     // second half of tile kt + NS - 1 -> stage of tile kt - 1
-    const bool dma1 = !(DBG & 2) && !LAST && kt + NS < nk;           // first half of tile kt + NS -> this tile's stage
+    const bool dma2 = kt >= 1 && kt + NS - 1 < nk;     // second half of tile kt + NS - 1 -> stage of tile kt - 1
+    const bool dma1 = !LAST && kt + NS < nk;           // first half of tile kt + NS -> this tile's stage
     auto fill_dma2 = [&](auto m_c) {
       constexpr int m = decltype(m_c)::value;
       if constexpr (m >= G0 && m - G0 < NP2) { if (dma2) issue1(kt + NS - 1, prv, std::integral_constant<int, NP1 + m - G0>{}); }
     };
     auto sync_next = [&]() {
-      if constexpr (!(DBG & 4)) {
-        if (NS >= 3 && kt + 2 < nk) wait_vmcnt<(NS >= 3 ? NS - 2 : 0) * NPW>(); else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-      }
+      if (NS >= 3 && kt + 2 < nk) wait_vmcnt<(NS >= 3 ? NS - 2 : 0) * NPW>(); else wait_vmcnt<0>();
+      __builtin_amdgcn_s_barrier();
     };
     auto fill_next = [&](auto m_c) {       // the next tile's first fragments + the first half of the DMA into the freed stage
       constexpr int m = decltype(m_c)::value;
@@ -674,7 +637,6 @@ __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
   }
   tile_body(nk - 1, cur, 0u, prv, std::true_type{});
 
-  if ((DBG & 1) && acc[0][0][0] != 12345.678f) return;
   if constexpr (CS) {
     if (do_cs) {
 #pragma unroll
@@ -727,7 +689,7 @@ __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
     }
     return;
   }
-  const bool wide_ok = p.pool == 0 && !(DBG & 128) && (p.ldc & 3) == 0 && (p.N & 3) == 0 &&
+  const bool wide_ok = p.pool == 0 && (p.ldc & 3) == 0 && (p.N & 3) == 0 &&
                        (!p.residual || (p.ldr & 3) == 0) && (p.act != PFPP_ACT_GEGLU || (p.N & 7) == 0);
   if (wide_ok) {
     __builtin_amdgcn_s_barrier();      // every wave is done with the DMA ring: its first bytes become the transposition patches
@@ -800,9 +762,9 @@ __global__ __launch_bounds__(256) void pl_reduce_group_kernel(const SlabGroupP g
   *dstp = s;
 }
 
-template <int MT, int NT, int WM, int WN, int NS, bool AK, bool WK, int DBG, bool AF = false, bool X1 = false, bool CS = false>
+template <int MT, int NT, int WM, int WN, int NS, bool AK, bool WK, bool AF = false, bool X1 = false, bool CS = false>
 __global__ __launch_bounds__(64 * WM * WN, (MT * NT >= 16 ? 1 : 2)) void gemm_pl_kernel(const GemmP p) {
-  pl_body<MT, NT, WM, WN, NS, AK, WK, DBG, AF, X1, CS>(p);
+  pl_body<MT, NT, WM, WN, NS, AK, WK, AF, X1, CS>(p);
 }
 
 // ---- grouped weight gradients: up to PFPP_DW_GROUP_MAX problems dW_j += dY_j^T . X_j (+ db_j += colsum dY_j) over the SAME contraction
@@ -827,62 +789,39 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_pl_dwgroup_kernel(const 
 #pragma unroll
   for (int k = 1; k < PFPP_DW_GROUP_MAX; ++k)
     if (k < g.n && t >= g.first_tile[k]) j = k;
-  pl_body<MT, NT, WM, WN, NS, true, true, 0, false, false, true, true>(g.p[j], t - g.first_tile[j]);
+  pl_body<MT, NT, WM, WN, NS, true, true, false, false, true, true>(g.p[j], t - g.first_tile[j]);
 }
 
 template <int MT, int NT, int WM, int WN, int NS>
 int launch_dwgroup(DwGroupP& g, const pfpp_dw_job* jobs, hipStream_t st) {
   using C = Cfg<MT, NT, WM, WN, NS, false>;
-  static unsigned long long attr_set = 0;      // one bit per device: the attribute belongs to the function ON a device
-  auto kern = gemm_pl_dwgroup_kernel<MT, NT, WM, WN, NS>;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!((attr_set >> (dev & 63)) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set |= 1ull << (dev & 63);
-  }
+  constexpr auto kern = gemm_pl_dwgroup_kernel<MT, NT, WM, WN, NS>;
+  (void)pfpp_allow_dyn_lds<kern>();
   int tiles = 0;
   for (int j = 0; j < g.n; ++j) {
     g.p[j].tiles_n = (int)((jobs[j].N + C::BN - 1) / C::BN);
     g.first_tile[j] = tiles;
     tiles += (int)((jobs[j].M + C::BM - 1) / C::BM) * g.p[j].tiles_n;
   }
-  snprintf(last_kernel, sizeof(last_kernel), "gemm_pl_dwgroup_kernel<%d, %d, %d, %d, %d>", MT, NT, WM, WN, NS);
+  static const KernelName name("gemm_pl_dwgroup_kernel<%d, %d, %d, %d, %d>", MT, NT, WM, WN, NS);
+  report_kernel(name);
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(C::NTHR), C::SMEM, st, g);
   return pfpp::check_launch("pfpp_gemm_dw_group");
 }
 
-template <int MT, int NT, int WM, int WN, int NS, bool AK = false, bool WK = false, int DBG = 0, bool AF = false, bool X1 = false, bool CS = false>
-int launch_pl(const GemmP& p0, int batch, hipStream_t st, int group_m, int splits = 1) {
+template <int MT, int NT, int WM, int WN, int NS, bool AK = false, bool WK = false, bool AF = false, bool X1 = false, bool CS = false>
+int launch_pl(const GemmP& p0, int batch, hipStream_t st, int splits = 1) {
   using C = Cfg<MT, NT, WM, WN, NS, X1>;
-#ifdef PFPP_PL_LAB
-  if constexpr (DBG == 0 && !AF && !X1) {
-    const char* e = getenv("PFPP_GEMM_DBG");
-    switch (e ? atoi(e) : 0) {
-      case 1: return launch_pl<MT, NT, WM, WN, NS, AK, WK, 1>(p0, batch, st, group_m, splits);
-      case 3: return launch_pl<MT, NT, WM, WN, NS, AK, WK, 3>(p0, batch, st, group_m, splits);
-      case 7: return launch_pl<MT, NT, WM, WN, NS, AK, WK, 7>(p0, batch, st, group_m, splits);
-      case 15: return launch_pl<MT, NT, WM, WN, NS, AK, WK, 15>(p0, batch, st, group_m, splits);
-      case 23: return launch_pl<MT, NT, WM, WN, NS, AK, WK, 23>(p0, batch, st, group_m, splits);
-      case 128: return launch_pl<MT, NT, WM, WN, NS, AK, WK, 128>(p0, batch, st, group_m, splits);
-      default: break;
-    }
-  }
-#endif
-  static bool attr_set = false;
-  auto kern = gemm_pl_kernel<MT, NT, WM, WN, NS, AK, WK, DBG, AF, X1, CS>;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = gemm_pl_kernel<MT, NT, WM, WN, NS, AK, WK, AF, X1, CS>;
+  (void)pfpp_allow_dyn_lds<kern>();
   GemmP p = p0;
   p.tiles_m = (p.M + C::BM - 1) / C::BM;
   p.tiles_n = (p.N + C::BN - 1) / C::BN;
-  p.group_m = p.tiles_n > 1 ? group_m : 0;
+  p.group_m = p.tiles_n > 1 ? GROUP_M : 0;
   const int nk_all = p.K / BK;
   p.split_k = splits < 1 ? 1 : (splits > nk_all ? nk_all : splits);
   const bool slabs = p.split_k > 1 && p.split_ws && batch == 1 && (p.N & 3) == 0 && (p.ldc & 3) == 0 && (!p.residual || (p.ldr & 3) == 0) &&
-                     (int64_t)p.split_k * p.M * (p.N + 1) * (int64_t)sizeof(float) <= p_ws_bytes;
+                     (int64_t)p.split_k * p.M * (p.N + 1) * (int64_t)sizeof(float) <= p.ws_bytes;
   if (!slabs) p.split_ws = nullptr;
   if constexpr (!CS) p.csum = nullptr;
   // partial column sums of the chunks live behind the C slabs (the capacity check of the caller includes them)
@@ -892,8 +831,11 @@ int launch_pl(const GemmP& p0, int batch, hipStream_t st, int group_m, int split
   }
   p.k_chunk = 0;
   const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * p.split_k), 1, (unsigned)batch);
-  snprintf(last_kernel, sizeof(last_kernel), "gemm_pl_kernel<%d, %d, %d, %d, %d, %s, %s, %d, %s, %s, %s>%s", MT, NT, WM, WN, NS, AK ? "true" : "false",
-           WK ? "true" : "false", DBG, AF ? "true" : "false", X1 ? "true" : "false", CS ? "true" : "false", slabs ? "+pl_reduce_kernel" : "");
+  // the eighth field is a constant 0, where a template parameter used to be: readers of this string index the flags by position
+  // (bench.py takes the arithmetic of a launch from the tenth)
+  static const KernelName name("gemm_pl_kernel<%d, %d, %d, %d, %d, %s, %s, 0, %s, %s, %s>", MT, NT, WM, WN, NS, AK ? "true" : "false",
+                               WK ? "true" : "false", AF ? "true" : "false", X1 ? "true" : "false", CS ? "true" : "false");
+  report_kernel(name, slabs ? "+pl_reduce_kernel" : "");
   hipLaunchKernelGGL(kern, grid, dim3(C::NTHR), C::SMEM + (AF ? 2048 : 0), st, p);
   if (p.defer) {
     pfpp_slab_job& q = *p.defer;
@@ -914,78 +856,69 @@ int launch_pl(const GemmP& p0, int batch, hipStream_t st, int group_m, int split
 }  // namespace pl
 
 // variant: 0 = pick by shape, 1 = 256x256 (8 waves of 128x64, 2 stages), 2 = 256x128 (8 waves, 3 stages), 3 = 128x128 (4 waves,
-// 2 stages, two workgroups per CU), 6 = 128x64 (3 stages): small tiles for narrow outputs
+// 2 stages, two workgroups per CU), 6 = 128x64 (3 stages): small tiles for narrow outputs, 11 = 64x32 (two waves, 3 stages; row-major
+// operands only, otherwise 128x64); any other value: 128x128
 // single-pass fp16 (hi planes only, one MFMA per product): the perf mode of BASELINE configs[4] — no fp32-grade guarantee
-static int launch_variant_x1(const GemmP& p, int batch, hipStream_t st, int group_m, int variant, int splits) {
+static int launch_variant_x1(const GemmP& p, int batch, hipStream_t st, int variant, int splits) {
   switch (variant) {
-    case 1: return pl::launch_pl<4, 2, 2, 4, 2, false, false, 0, false, true>(p, batch, st, group_m, splits);
-    case 2: return pl::launch_pl<2, 2, 4, 2, 3, false, false, 0, false, true>(p, batch, st, group_m, splits);
-    case 6: return pl::launch_pl<2, 1, 2, 2, 3, false, false, 0, false, true>(p, batch, st, group_m, splits);
-    default: return pl::launch_pl<2, 2, 2, 2, 2, false, false, 0, false, true>(p, batch, st, group_m, splits);
+    case 1: return pl::launch_pl<4, 2, 2, 4, 2, false, false, false, true>(p, batch, st, splits);
+    case 2: return pl::launch_pl<2, 2, 4, 2, 3, false, false, false, true>(p, batch, st, splits);
+    case 6: return pl::launch_pl<2, 1, 2, 2, 3, false, false, false, true>(p, batch, st, splits);
+    default: return pl::launch_pl<2, 2, 2, 2, 2, false, false, false, true>(p, batch, st, splits);
   }
 }
 
 template <bool AK, bool WK>
-static int launch_variant(const GemmP& p, int batch, hipStream_t st, int group_m, int variant, int splits) {
+static int launch_variant(const GemmP& p, int batch, hipStream_t st, int variant, int splits) {
   if constexpr (AK && WK) {
     if (p.csum) {      // dW = dY^T . X with the bias gradient (column sums of dY) computed on the way
       switch (variant) {
-        case 1: case 2: return pl::launch_pl<2, 2, 4, 2, 3, AK, WK, 0, false, false, true>(p, batch, st, group_m, splits);
-        case 6: return pl::launch_pl<2, 1, 2, 2, 3, AK, WK, 0, false, false, true>(p, batch, st, group_m, splits);
-        default: return pl::launch_pl<2, 2, 2, 2, 2, AK, WK, 0, false, false, true>(p, batch, st, group_m, splits);
+        case 1: case 2: return pl::launch_pl<2, 2, 4, 2, 3, AK, WK, false, false, true>(p, batch, st, splits);
+        case 6: return pl::launch_pl<2, 1, 2, 2, 3, AK, WK, false, false, true>(p, batch, st, splits);
+        default: return pl::launch_pl<2, 2, 2, 2, 2, AK, WK, false, false, true>(p, batch, st, splits);
       }
     }
   }
   switch (variant) {
     case 1:
-      if constexpr (!AK && !WK) return pl::launch_pl<4, 2, 2, 4, 2, AK, WK>(p, batch, st, group_m, splits);
+      if constexpr (!AK && !WK) return pl::launch_pl<4, 2, 2, 4, 2, AK, WK>(p, batch, st, splits);
       [[fallthrough]];
-    case 2: return pl::launch_pl<2, 2, 4, 2, 3, AK, WK>(p, batch, st, group_m, splits);
-    case 6: return pl::launch_pl<2, 1, 2, 2, 3, AK, WK>(p, batch, st, group_m, splits);
-    case 9:       // 64 x 64 (4 waves of 32 x 32, three stages): grids of a few dozen workgroups — twice the workgroups per output, half
-                  // the bytes per K-tile of each: a single puzzle's 200-row GEMMs are bound by the per-workgroup DMA rate
-      if constexpr (!AK && !WK) return pl::launch_pl<1, 1, 2, 2, 3, AK, WK>(p, batch, st, group_m, splits);
-      return pl::launch_pl<2, 1, 2, 2, 3, AK, WK>(p, batch, st, group_m, splits);
-    case 10:      // 128 x 32, two waves: twice the workgroups along N, each streaming half the weight columns
-      if constexpr (!AK && !WK) return pl::launch_pl<2, 1, 2, 1, 3, AK, WK>(p, batch, st, group_m, splits);
-      return pl::launch_pl<2, 1, 2, 2, 3, AK, WK>(p, batch, st, group_m, splits);
+    case 2: return pl::launch_pl<2, 2, 4, 2, 3, AK, WK>(p, batch, st, splits);
+    case 6: return pl::launch_pl<2, 1, 2, 2, 3, AK, WK>(p, batch, st, splits);
     case 11:      // 64 x 32, two waves
-      if constexpr (!AK && !WK) return pl::launch_pl<1, 1, 2, 1, 3, AK, WK>(p, batch, st, group_m, splits);
-      return pl::launch_pl<2, 1, 2, 2, 3, AK, WK>(p, batch, st, group_m, splits);
-    case 12:      // 64 x 64 as two waves of 32 x 64: the GEGLU form (value | gate column tiles in one wave) of the above
-      if constexpr (!AK && !WK) return pl::launch_pl<1, 2, 2, 1, 3, AK, WK>(p, batch, st, group_m, splits);
-      return pl::launch_pl<2, 2, 2, 2, 2, AK, WK>(p, batch, st, group_m, splits);
-    default: return pl::launch_pl<2, 2, 2, 2, 2, AK, WK>(p, batch, st, group_m, splits);
+      if constexpr (!AK && !WK) return pl::launch_pl<1, 1, 2, 1, 3, AK, WK>(p, batch, st, splits);
+      return pl::launch_pl<2, 1, 2, 2, 3, AK, WK>(p, batch, st, splits);
+    default: return pl::launch_pl<2, 2, 2, 2, 2, AK, WK>(p, batch, st, splits);
   }
 }
 
 // fp32 A read in place (LDS-DMA of fp32 rows, converted when a wave fetches its fragments) with the train-mode BatchNorm + ReLU of
 // the previous set-abstraction layer fused in: the [1.26 M x 64..256] encoder GEMMs, bound by HBM, not by the conversions
-int launch_f16x3_planes_af32(const GemmP& p0, int batch, hipStream_t st, int group_m) {
-  GemmP p = p0;
-  if (getenv("PFPP_DIAG_NO_STATS")) p.stats = nullptr;       // diagnostic only: what do the statistics atomics cost?
-  if (getenv("PFPP_DIAG_NO_POOL")) { p.pool = 0; p.Cmin = nullptr; }
+int launch_f16x3_planes_af32(const GemmP& p, int batch, hipStream_t st) {
   // measured on the train-mode set-abstraction shapes (tools/diag/gemm_calls.py): every tile / stage choice lands within 10 % — these
   // launches are bound by the per-workgroup fixed costs of a 2..8 K-tile contraction (cold-HBM prologue, epilogue) and by HBM
   // itself (3.6 TB/s on the layers that write their activation), not by the K loop.  Two or three co-resident workgroups per CU
   // hide a little more of the prologue than one large one.
-  static const int afv = getenv("PFPP_GEMM_AF32_VARIANT") ? atoi(getenv("PFPP_GEMM_AF32_VARIANT")) : 0;
-  if (afv == 4) return pl::launch_pl<2, 2, 4, 2, 3, false, false, 0, true>(p, batch, st, group_m, 1);       // 256 x 128, one per CU
-  if (p.N <= 64) return pl::launch_pl<2, 1, 2, 2, 2, false, false, 0, true>(p, batch, st, group_m, 1);      // 128 x 64, three per CU
-  return pl::launch_pl<2, 2, 2, 2, 2, false, false, 0, true>(p, batch, st, group_m, 1);                      // 128 x 128, two per CU
+  if (p.N <= 64) return pl::launch_pl<2, 1, 2, 2, 2, false, false, true>(p, batch, st, 1);      // 128 x 64, three per CU
+  return pl::launch_pl<2, 2, 2, 2, 2, false, false, true>(p, batch, st, 1);                      // 128 x 128, two per CU
 }
 
 // Tile and K split from a small cost model fitted to tools/gemm_lab measurements on 3,850-row shapes: a workgroup's main
 // loop is bound by operand delivery (~45 GB/s of L2 -> LDS DMA per CU, shared by co-resident workgroups) or by its MFMAs
 // (32 cycles each, ~75 % sustained); the epilogue streams C once (3.5 TB/s) — or, for a K split, writes and re-reads one
 // slab per chunk plus a second launch (6 us); atomics onto a shared C run at 1.2 TB/s.  fix_variant / fix_splits != 0 pin a choice.
-static void pl_choose(int M, int N, int K, int fix_variant, int fix_splits, bool have_ws, int64_t ws_bytes, bool accumulate, bool no_v6,
-                      int* out_v, int* out_s, bool allow_v1 = false, bool tn_form = false) {
+// (The dW form — both operands k-major, two transposing LDS reads per MFMA operand — measures 20-25 % above this model's delivery
+// bound on the two-stage 128 x 128 tile: 1536x512x3850 40.3 us vs 32.1 us for the three-stage 128 x 64 tile at the same split.  A
+// penalty for it is right stand-alone — serial iteration 9.55 -> 9.33 ms — but it moves the weight gradients to the 144 KB-LDS
+// 256 x 128 tile, which then owns whole CUs next to the main chain: overlapped iteration 8.30 -> 8.57 ms.  Not modelled.)
+struct PlChoice { int variant, splits; };
+static PlChoice pl_choose(int M, int N, int K, int fix_variant, int fix_splits, bool have_ws, int64_t ws_bytes, bool accumulate, bool no_v6,
+                          bool allow_v1) {
   const int nk = K / 32;
   const int cand_v[4] = {2, 3, 6, 1};
   const int cand_s[9] = {1, 2, 3, 4, 6, 8, 10, 12, 16};
   double best = 1e30;
-  int best_v = 3, best_s = 1;
+  PlChoice c{3, 1};
   for (int vi = 0; vi < 4; ++vi) {
     const int v = cand_v[vi];
     if (fix_variant != 0 && v != fix_variant) continue;
@@ -1012,45 +945,26 @@ static void pl_choose(int M, int N, int K, int fix_variant, int fix_splits, bool
       if (slabs) t_epi = (2.0 * sp * cbytes + (accumulate ? 2.0 : 1.0) * cbytes) / 3.5e12 + 6e-6;      // + the reduction launch (6.6 us measured)
       else if (accumulate) t_epi = sp * cbytes / 1.2e12;
       else t_epi = cbytes / 3.5e12;
-      double t_loop = t_bw > t_mma ? t_bw : t_mma;
-      // dW form (both operands k-major: two transposing LDS reads per MFMA operand): the two-stage 128 x 128 tile measures 20-25 %
-      // above its delivery bound there (1536x512x3850: 40.3 us vs 32.1 us for the three-stage 128 x 64 tile at the same split)
-      // (off by default: stand-alone it is right — serial iteration 9.55 -> 9.33 ms — but it moves the weight gradients to the
-      // 144 KB-LDS 256 x 128 tile, which then owns whole CUs next to the main chain: overlapped iteration 8.30 -> 8.57 ms)
-      static const bool tn_pen = getenv("PFPP_PL_TN_PENALTY") && atoi(getenv("PFPP_PL_TN_PENALTY")) == 1;
-      if (tn_form && v == 3 && tn_pen) t_loop *= 1.25;
-      const double t = t_loop + t_epi + 4e-6;
-      if (t < best) { best = t; best_v = v; best_s = sp; }
+      const double t = (t_bw > t_mma ? t_bw : t_mma) + t_epi + 4e-6;
+      if (t < best) { best = t; c = PlChoice{v, sp}; }
     }
   }
-  *out_v = best_v;
-  *out_s = best_s;
-  static const bool dbg = getenv("PFPP_GEMM_CHOICE_DEBUG") != nullptr;
-  if (dbg) fprintf(stderr, "pl_choose M%d N%d K%d -> variant %d splits %d (model %.1f us)\n", M, N, K, best_v, best_s, best * 1e6);
+  return c;
 }
 
-int launch_f16x3_planes(const GemmP& p, int batch, hipStream_t st, int group_m, int variant) {
-  pl::p_ws_bytes = p.split_ws ? p.ws_bytes : 0;
-  // few output tiles and an epilogue the slab reduction can express (bias / activation / residual, fp32 out): split the
-  // contraction over the idle CUs — the 100..500-row GEMMs of a single puzzle's DDPM step (16 tiles x 16 K-tiles otherwise)
-  if (variant == 0 && batch == 1 && p.split_ws && !p.x1 && p.pool == 0 && !p.stats && !p.scale && !p.Chi && !p.Cmin &&
-      p.act != PFPP_ACT_GEGLU && (p.N & 3) == 0 && (p.ldc & 3) == 0 && (!p.residual || (p.ldr & 3) == 0) &&
-      (int64_t)((p.M + 127) / 128) * ((p.N + 63) / 64) <= 96) {
-    // measured on the single-puzzle loop (bench.aggl_puzzles_per_s, one puzzle in flight): 5.28 -> 4.86 puzzles/s — the slab epilogues
-    // and the second launch cost more than the shorter K loops save; off unless asked for
-    static const bool on = getenv("PFPP_GEMM_SMALL_SPLIT") && atoi(getenv("PFPP_GEMM_SMALL_SPLIT")) == 1;
-    if (on) {
-      int v = 3, sp = 1;
-      pl_choose(p.M, p.N, p.K, 0, 0, true, pl::p_ws_bytes, false, false, &v, &sp);
-      if (sp > 1) return launch_variant<false, false>(p, batch, st, group_m, v, sp);
-    }
-  }
-  static const int chooser = getenv("PFPP_GEMM_CHOOSER") ? atoi(getenv("PFPP_GEMM_CHOOSER")) : 1;      // 0: tile-count rule; 2: no 256 x 256
-  if (chooser && variant == 0 && batch == 1 && !p.x1 && p.pool == 0 && !p.stats && p.M <= 16384) {
-    // token-sized GEMMs of the transformer: the same cost model as pfpp_gemm_planes (tile only; no K split on this path)
-    int v = 3, sp = 1;
-    pl_choose(p.M, p.N, p.K, 0, 1, false, 0, false, p.act == PFPP_ACT_GEGLU, &v, &sp, chooser != 2);
-    variant = v;
+// a single puzzle's GEMMs (200 rows): each workgroup streams its weight columns cold (57.6 M parameters do not stay in L2 between
+// steps) at the per-workgroup DMA rate, so narrower tiles = more workgroups pulling in parallel: one puzzle in flight 5.1-5.3 ->
+// 5.4-5.5 puzzles/s with the 64 x 32 tile (64 x 64: no gain, same columns per workgroup)
+constexpr int TINY_TILE_VARIANT = 11;
+
+// Tile (a launch_variant value) of a pfpp_gemm call with a pre-split A — a function of the problem alone.  No K split on this path: for the
+// 100..500-row GEMMs of a single puzzle's DDPM step a split over the idle CUs measured 5.28 -> 4.86 puzzles/s
+// (bench.aggl_puzzles_per_s, one puzzle in flight) — the slab epilogues and the second launch cost more than the shorter K loops save.
+static int choose_planes_variant(const GemmP& p, int batch) {
+  int variant = 0;
+  if (batch == 1 && !p.x1 && p.pool == 0 && !p.stats && p.M <= 16384) {
+    // token-sized GEMMs of the transformer: the same cost model as pfpp_gemm_planes (tile only)
+    variant = pl_choose(p.M, p.N, p.K, 0, 1, false, 0, false, p.act == PFPP_ACT_GEGLU, true).variant;
   }
   if (variant == 0) {
     const int64_t t256 = ((int64_t)(p.M + 255) / 256) * ((p.N + 255) / 256) * batch;
@@ -1059,21 +973,18 @@ int launch_f16x3_planes(const GemmP& p, int batch, hipStream_t st, int group_m, 
     variant = t256 >= 512 ? 1 : (t21 >= 160 ? 2 : (t11 >= 200 ? 3 : 6));
     // (a six-stage ring for grids of a few workgroups was tried for the single-puzzle loop: 5.50 -> 5.55 puzzles/s, not kept)
   }
-  // a single puzzle's GEMMs (200 rows): each workgroup streams its weight columns cold (57.6 M parameters do not stay in L2 between
-  // steps) at the per-workgroup DMA rate, so narrower tiles = more workgroups pulling in parallel: one puzzle in flight 5.1-5.3 ->
-  // 5.4-5.5 puzzles/s with the 64 x 32 tile (9 = 64 x 64: no gain, same columns per workgroup; 0 = keep 128 x 64)
-  static const int tiny = getenv("PFPP_GEMM_TINY_TILE") ? atoi(getenv("PFPP_GEMM_TINY_TILE")) : 11;
-  if (tiny && variant == 6 && batch == 1 && !p.x1 && p.pool == 0 && p.act != PFPP_ACT_GEGLU &&
-      (int64_t)((p.M + 127) / 128) * ((p.N + 63) / 64) <= 48)
-    variant = tiny;
-  static const int tiny_g = getenv("PFPP_GEMM_TINY_GEGLU") ? atoi(getenv("PFPP_GEMM_TINY_GEGLU")) : 0;
-  if (tiny_g && batch == 1 && !p.x1 && p.pool == 0 && p.act == PFPP_ACT_GEGLU && (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128) <= 96)
-    variant = 12;
+  if (variant == 6 && batch == 1 && !p.x1 && p.pool == 0 && p.act != PFPP_ACT_GEGLU && (int64_t)((p.M + 127) / 128) * ((p.N + 63) / 64) <= 48)
+    variant = TINY_TILE_VARIANT;
   // GEGLU gates pairs of column tiles (two per wave at least); the pool = 64 epilogue needs two row tiles per wave
   if (variant == 6 && p.act == PFPP_ACT_GEGLU) variant = 3;
   if (variant == 1 && p.pool == 64) variant = 2;
-  if (p.x1) return launch_variant_x1(p, batch, st, group_m, variant, 1);
-  return launch_variant<false, false>(p, batch, st, group_m, variant, 1);
+  return variant;
+}
+
+int launch_f16x3_planes(const GemmP& p, int batch, hipStream_t st) {
+  const int variant = choose_planes_variant(p, batch);
+  if (p.x1) return launch_variant_x1(p, batch, st, variant, 1);
+  return launch_variant<false, false>(p, batch, st, variant, 1);
 }
 
 }  // namespace pfpp_gemm_detail
@@ -1126,13 +1037,11 @@ extern "C" int pfpp_gemm_dw_group(const pfpp_dw_job* jobs, int32_t n_jobs, int64
     p.csum = q.gb; p.csum_alpha = 1.0f / q.dy.scale;
   }
   hipStream_t st = pfpp::as_stream(stream);
-  const int env_v = getenv("PFPP_DW_GROUP_VARIANT") ? atoi(getenv("PFPP_DW_GROUP_VARIANT")) : 0;      // (read per call, like PFPP_TRAIN_DW_GROUP*: the tests switch it)
   // default: the 256 x 128 tile (8 waves, one workgroup per CU).  Measured on a block's six problems at 3,850 tokens
   // (profiles/r05a_lab_dw_group_bench.txt): 166 us against 195-213 us for the 128 x 64 / 128 x 128 tiles (and 256 us for six separate
   // launches + their slab reductions) although its 160 tiles leave 96 CUs without one; in the overlapped training iteration 6.06 ms
   // against 6.28 (small tiles) and 6.23 (separate launches) — profiles/r05a_ab_dwgroup.txt
-  const int v = variant ? variant : (env_v ? env_v : 2);
-  switch (v) {
+  switch (variant ? variant : 2) {
     case 6: return pl::launch_dwgroup<2, 1, 2, 2, 3>(g, jobs, st);       // 128 x 64, three stages (72 KB: two workgroups per CU)
     case 7: return pl::launch_dwgroup<2, 1, 2, 2, 2>(g, jobs, st);       // 128 x 64, two stages (48 KB: three per CU)
     case 2: return pl::launch_dwgroup<2, 2, 4, 2, 3>(g, jobs, st);       // 256 x 128, 8 waves
@@ -1164,29 +1073,24 @@ extern "C" int pfpp_gemm_planes(const pfpp_gemm_planes_args* a, pfpp_stream_t st
   p.act = a->act; p.zdiv = 1; p.alpha = a->alpha; p.accum = a->accumulate ? 1 : 0;
   p.split_ws = a->ws;
   p.ws_bytes = a->ws ? a->ws_bytes : 0;
-  pl::p_ws_bytes = p.ws_bytes;
   PFPP_SUPPORTED(!a->colsum || (a->a_kmajor && a->w_kmajor && !a->single_pass), "colsum rides with the k-major pair (dW = dY^T . X) only");
   p.csum = a->colsum; p.csum_alpha = a->colsum_alpha;
   PFPP_SUPPORTED(!a->defer || (!a->bias && !a->residual && a->act == PFPP_ACT_NONE && a->ws), "defer: plain (accumulating) outputs with a workspace only");
   p.defer = a->defer;
   hipStream_t st = pfpp::as_stream(stream);
   int variant = a->variant, splits = a->splits;
-  const int nk = p.K / 32;
   if (variant == 0 || splits == 0) {
-    int best_v = 3, best_s = 1;
-    pl_choose(p.M, p.N, p.K, a->variant, a->splits, a->ws != nullptr, a->ws ? a->ws_bytes : 0, a->accumulate != 0, false, &best_v, &best_s,
-              !a->a_kmajor && !a->w_kmajor && !a->single_pass, a->a_kmajor && a->w_kmajor);
-    if (variant == 0) variant = best_v;
-    if (splits == 0) splits = best_s;
+    const PlChoice c = pl_choose(p.M, p.N, p.K, a->variant, a->splits, a->ws != nullptr, p.ws_bytes, a->accumulate != 0, false,
+                                 !a->a_kmajor && !a->w_kmajor && !a->single_pass);
+    if (variant == 0) variant = c.variant;
+    if (splits == 0) splits = c.splits;
   }
-  static const int gm_env = getenv("PFPP_GEMM_GROUP_M") ? atoi(getenv("PFPP_GEMM_GROUP_M")) : 8;
-  const int gm = gm_env;
   if (a->single_pass) {
     PFPP_SUPPORTED(!a->a_kmajor && !a->w_kmajor, "single-pass fp16 with k-major operands");
     p.x1 = 1;
-    return launch_variant_x1(p, 1, st, gm, variant, splits);
+    return launch_variant_x1(p, 1, st, variant, splits);
   }
-  if (a->a_kmajor) return launch_variant<true, true>(p, 1, st, gm, variant, splits);
-  if (a->w_kmajor) return launch_variant<false, true>(p, 1, st, gm, variant, splits);
-  return launch_variant<false, false>(p, 1, st, gm, variant, splits);
+  if (a->a_kmajor) return launch_variant<true, true>(p, 1, st, variant, splits);
+  if (a->w_kmajor) return launch_variant<false, true>(p, 1, st, variant, splits);
+  return launch_variant<false, false>(p, 1, st, variant, splits);
 }

@@ -233,12 +233,7 @@ extern "C" int pfpp_gemm_small(const pfpp_planes* A, int64_t lda, const pfpp_pw*
     return pfpp::check_launch(__func__);
   }
   const size_t smem = (size_t)2 * 2 * 32 * LKP * sizeof(_Float16);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return pfpp::check_launch(__func__);
-    attr_set = true;
-  }
+  if (pfpp_allow_dyn_lds<gemm_small_kernel>((int)smem) != hipSuccess) return pfpp::check_launch(__func__);
   const dim3 grid((unsigned)((M + 31) / 32), (unsigned)((N / 32 + 3) / 4));
   hipLaunchKernelGGL(gemm_small_kernel, grid, dim3(256), smem, pfpp::as_stream(stream), p);
   return pfpp::check_launch(__func__);

@@ -19,18 +19,16 @@
 // Arithmetic: the three split-f16 products of a 16-deep step in the order lo.hi, hi.lo, hi.hi, k ascending, one accumulator chain per
 // output, epilogue (acc * alpha + bias) + residual — gemm_pl_kernel's, bit for bit (tested).
 #include <stdlib.h>
-#include <type_traits>
-#include <utility>
 
+#include "lds_asm.h"
 #include "pfpp_common.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+using namespace pfpp_lds;
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 struct WdP {
   const _Float16 *ah, *al; int64_t lda;      // planes of a_scale * A [M, K]
@@ -42,24 +40,12 @@ struct WdP {
   int M, N, K;
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int OFF>
-__device__ __forceinline__ half8 lds_rd(uint32_t addr) {
-  half8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
 template <int OFF>
 __device__ __forceinline__ half8 gld(const half8* p) {
   half8 v;
   asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(v) : "v"(p), "n"(OFF) : "memory");
   return v;
 }
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
 template <int MT, int NT, int D, bool X1 = false>
 struct WdCfg {
@@ -419,15 +405,10 @@ __global__ __launch_bounds__(256) void reblock_kernel(const RbP p) {
 template <int MT, int NT, int D, bool X1 = false, bool PF = false>
 int launch_wd(const WdP& p, hipStream_t st) {
   using C = WdCfg<MT, NT, D, X1>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fn;
-    if constexpr (PF) fn = (const void*)gemm_wd_pf_kernel<MT, NT, D>;
-    else fn = (const void*)gemm_wd_kernel<MT, NT, D, X1>;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::SMEM) != hipSuccess)
-      return pfpp::check_launch("pfpp_gemm_wd");
-    attr_set = true;
-  }
+  hipError_t attr;
+  if constexpr (PF) attr = pfpp_allow_dyn_lds<gemm_wd_pf_kernel<MT, NT, D>>((int)C::SMEM);
+  else attr = pfpp_allow_dyn_lds<gemm_wd_kernel<MT, NT, D, X1>>((int)C::SMEM);
+  if (attr != hipSuccess) return pfpp::check_launch("pfpp_gemm_wd");
   const unsigned tiles = (unsigned)(((p.M + C::BM - 1) / C::BM) * (p.N / C::BN));
   if constexpr (PF) hipLaunchKernelGGL((gemm_wd_pf_kernel<MT, NT, D>), dim3(tiles), dim3(256), C::SMEM, st, p);
   else hipLaunchKernelGGL((gemm_wd_kernel<MT, NT, D, X1>), dim3(tiles), dim3(256), C::SMEM, st, p);

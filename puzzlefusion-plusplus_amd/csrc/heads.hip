@@ -476,12 +476,7 @@ extern "C" int pfpp_heads_fwd(const float* pooled, const pfpp_head_params* trans
   PFPP_REQUIRE(fill_head(p.w[0], *trans, 3, 0) && fill_head(p.w[1], *rot, 4, 3), "null weight pointer");
   p.x = pooled; p.a0 = a0; p.v0 = v0; p.a1 = a1; p.v1 = v1; p.out = out; p.slot = slot; p.ldo = (int)ldo; p.R = (int)R;
   const size_t smem = (size_t)2 * 32 * KP * sizeof(_Float16);
-  static bool attr_set = false;
-  if (!attr_set) {                                       // 65 KB of dynamic LDS: above the default cap
-    if (hipFuncSetAttribute((const void*)heads_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return pfpp::check_launch(__func__);
-    attr_set = true;
-  }
+  if (pfpp_allow_dyn_lds<heads_fwd_kernel>((int)smem) != hipSuccess) return pfpp::check_launch(__func__);      // 65 KB of dynamic LDS: above the default cap
   hipLaunchKernelGGL(heads_fwd_kernel, dim3((unsigned)((R + 31) / 32), 2), dim3(64 * NW), smem, pfpp::as_stream(stream), p);
   return pfpp::check_launch(__func__);
 }
@@ -504,12 +499,7 @@ extern "C" int pfpp_heads_bwd(const float* dout, const int32_t* slot, const pfpp
   p.dout = dout; p.slot = slot; p.a0 = a0; p.v0 = v0; p.a1 = a1; p.v1 = v1; p.da0 = da0; p.da1 = da1; p.dp = dp; p.G = grad_scale; p.R = (int)R;
   hipStream_t st = pfpp::as_stream(stream);
   const size_t smem = (size_t)2 * 32 * KP * sizeof(_Float16) + (size_t)NW * 8192;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)heads_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return pfpp::check_launch(__func__);
-    attr_set = true;
-  }
+  if (pfpp_allow_dyn_lds<heads_bwd_kernel>((int)smem) != hipSuccess) return pfpp::check_launch(__func__);
   hipLaunchKernelGGL(heads_bwd_kernel, dim3((unsigned)((R + 31) / 32), 2), dim3(64 * NW), smem, st, p);
   if (dx) {
     const int64_t total = R * L * C;

@@ -286,13 +286,8 @@ extern "C" int pfpp_layernorm_linear_small(const float* x, const float* mod, int
   p.units_per_group = upg;
   const dim3 grid((unsigned)row_tiles, (unsigned)((n_units + upg - 1) / upg));
   hipStream_t st = pfpp::as_stream(stream);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)lnlin_small_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-        hipFuncSetAttribute((const void*)lnlin_small_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return pfpp::check_launch(__func__);
-    attr_set = true;
-  }
+  if ((u_planes ? pfpp_allow_dyn_lds<lnlin_small_kernel<true>>((int)smem) : pfpp_allow_dyn_lds<lnlin_small_kernel<false>>((int)smem)) != hipSuccess)
+    return pfpp::check_launch(__func__);
   if (u_planes) hipLaunchKernelGGL(lnlin_small_kernel<true>, grid, dim3(64 * LNW), smem, st, p);
   else hipLaunchKernelGGL(lnlin_small_kernel<false>, grid, dim3(64 * LNW), smem, st, p);
   return pfpp::check_launch(__func__);

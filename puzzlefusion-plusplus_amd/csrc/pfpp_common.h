@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <stdio.h>
 
 #include "pfpp.h"
@@ -97,6 +98,20 @@ __host__ __device__ __forceinline__ uint64_t pfpp_rng_u64(uint64_t seed, uint32_
 inline uint32_t pfpp_drop_thresh(float p) {
   const double t = (double)p * 4294967296.0;
   return t <= 0.0 ? 0u : (t >= 4294967295.0 ? 4294967295u : (uint32_t)t);
+}
+
+// A kernel that takes more dynamic LDS than the default cap has to be allowed to, once.  The attribute belongs to the function
+// ON a device, so the "done" mask holds one bit per device; KERN is a template argument, so every kernel has its own mask.
+template <auto KERN>
+inline hipError_t pfpp_allow_dyn_lds(int bytes = 160 * 1024) {
+  static std::atomic<unsigned long long> done{0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (done.load(std::memory_order_relaxed) & bit) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.fetch_or(bit, std::memory_order_relaxed);
+  return e;
 }
 
 #define PFPP_REQUIRE(cond, msg)                                   \

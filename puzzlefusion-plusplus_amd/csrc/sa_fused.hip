@@ -480,12 +480,8 @@ extern "C" int pfpp_sa_mlp2_fused_p(const float* feats, const float* xyz, const 
   p.N = (int)N; p.S = (int)S; p.G = (int)(F * S);
   constexpr int d = 128, c1 = 128, c2 = 128;
   constexpr size_t smem = (size_t)2 * (c1 * ((d / 16 + 1) * 16 + 8) + c2 * (c1 + 8)) * sizeof(_Float16) + (size_t)2 * (c1 + c2) * sizeof(float);
-  auto kern = sa_mlp2_kernel<d, c1, c2>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  constexpr auto kern = sa_mlp2_kernel<d, c1, c2>;
+  (void)pfpp_allow_dyn_lds<kern>((int)smem);
   const int64_t wgs_needed = (p.G + 3) / 4;
   const unsigned grid = (unsigned)(wgs_needed < 256 ? wgs_needed : 256);      // persistent: one 4-wave workgroup per CU
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, pfpp::as_stream(stream), p);

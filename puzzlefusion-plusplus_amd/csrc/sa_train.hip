@@ -1291,12 +1291,8 @@ extern "C" int pfpp_sa_train_stage(const pfpp_sa_train_args* a, pfpp_stream_t st
     if (cap < n_slices) cap = n_slices;
     constexpr size_t smem_128 = (size_t)2 * 128 * (128 + 8) * sizeof(_Float16) + (2 + 4 + 3) * 128 * sizeof(float);
     constexpr size_t smem_256 = (size_t)2 * 128 * (256 + 8) * sizeof(_Float16) + (2 + 4 + 3) * 256 * sizeof(float);
-    static bool attr_u = false;
-    if (!attr_u) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa_wide_train_kernel<128, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_128);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa_wide_train_kernel<256, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_256);
-      attr_u = true;
-    }
+    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<128, 2, true>>((int)smem_128);
+    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<256, 2, true>>((int)smem_256);
     if (a->D == 128) hipLaunchKernelGGL((sa_wide_train_kernel<128, 2, true>), dim3((unsigned)cap), dim3(256), smem_128, st, p, (const float*)nullptr, n_total);
     else hipLaunchKernelGGL((sa_wide_train_kernel<256, 2, true>), dim3((unsigned)cap), dim3(256), smem_256, st, p, (const float*)nullptr, n_total);
     return pfpp::check_launch("pfpp_sa_train_stage");
@@ -1329,13 +1325,9 @@ extern "C" int pfpp_sa_train_stage(const pfpp_sa_train_args* a, pfpp_stream_t st
     const unsigned grid = (unsigned)cap;
     constexpr size_t smem_g = (size_t)2 * 128 * ((256 / 16 + 1) * 16 + 8) * sizeof(_Float16) + 2 * 256 * sizeof(float);
     constexpr size_t smem_r = (size_t)2 * 128 * (256 + 8) * sizeof(_Float16) + 2 * 256 * sizeof(float);
-    static bool attr_w = false;
-    if (!attr_w) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa_wide_train_kernel<256, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_g);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa_wide_train_kernel<256, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_r);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa_wide_train_kernel<256, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_r);
-      attr_w = true;
-    }
+    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<256, 1>>((int)smem_g);
+    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<256, 2>>((int)smem_r);
+    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<256, 3>>((int)smem_r);
     hipStream_t st = pfpp::as_stream(stream);
     if (L == 1) hipLaunchKernelGGL((sa_wide_train_kernel<256, 1>), dim3(grid), dim3(256), smem_g, st, p, a->y_in, n_total);
     else if (L == 2) hipLaunchKernelGGL((sa_wide_train_kernel<256, 2>), dim3(grid), dim3(256), smem_r, st, p, a->y_in, n_total);
@@ -1388,14 +1380,10 @@ extern "C" int pfpp_sa_train_stage(const pfpp_sa_train_args* a, pfpp_stream_t st
     constexpr size_t smem2 = smem1 + (size_t)2 * c2 * (c1 + 8) * sizeof(_Float16) + (size_t)3 * c1 * sizeof(float);
     constexpr int c3 = 256;
     constexpr size_t smem3 = (size_t)2 * c3 * (c2 + 8) * sizeof(_Float16) + (size_t)2 * c2 * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa_rows_train_kernel<c2, c3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa_rows8_train_kernel<c2, c3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa2_train_kernel<d, c1, c2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa2_train_kernel<d, c1, c2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-      attr_set = true;
-    }
+    (void)pfpp_allow_dyn_lds<sa_rows_train_kernel<c2, c3>>((int)smem3);
+    (void)pfpp_allow_dyn_lds<sa_rows8_train_kernel<c2, c3>>((int)smem3);
+    (void)pfpp_allow_dyn_lds<sa2_train_kernel<d, c1, c2, 1>>((int)smem1);
+    (void)pfpp_allow_dyn_lds<sa2_train_kernel<d, c1, c2, 2>>((int)smem2);
     PFPP_SUPPORTED(!a->sched || a->stage == 3, "stages 1 and 2 take the padding schedule only in their table-fed form (u_in)");
     if (a->stage == 1) hipLaunchKernelGGL((sa2_train_kernel<d, c1, c2, 1>), dim3(grid), dim3(256), smem1, st, p);
     else if (a->stage == 2) hipLaunchKernelGGL((sa2_train_kernel<d, c1, c2, 2>), dim3(grid), dim3(256), smem2, st, p);
@@ -1439,11 +1427,7 @@ extern "C" int pfpp_sa_mlp2_table_p(const float* u, const float* new_xyz, const 
   const int64_t need = (p.G + 3) / 4;
   if (need < cap) cap = need;
   constexpr size_t smem = (size_t)2 * 128 * (128 + 8) * sizeof(_Float16) + (2 + 4 + 3) * 128 * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa_wide_train_kernel<128, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr = true;
-  }
+  (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<128, 2, true, true>>((int)smem);
   hipLaunchKernelGGL((sa_wide_train_kernel<128, 2, true, true>), dim3((unsigned)cap), dim3(256), smem, pfpp::as_stream(stream), p, (const float*)nullptr, 128);
   return pfpp::check_launch("pfpp_sa_mlp2_table_p");
 }

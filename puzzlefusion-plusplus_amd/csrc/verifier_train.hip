@@ -409,14 +409,9 @@ extern "C" int pfpp_verifier_attn_bwd(const float* qkv, const float* out, const 
   PFPP_SUPPORTED(E >= 1 && E <= VA_MAXE, "1 <= E <= 256 tokens per sequence");
   if (B == 0) return PFPP_OK;
   const size_t lds = vattn_bwd_lds(E);
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(vattn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)vattn_bwd_lds(VA_MAXE)) != hipSuccess) {
-      pfpp::set_error("%s: hipFuncSetAttribute failed", __func__);
-      return PFPP_EHIP;
-    }
-    attr_set = true;
+  if (pfpp_allow_dyn_lds<vattn_bwd_kernel>((int)vattn_bwd_lds(VA_MAXE)) != hipSuccess) {
+    pfpp::set_error("%s: hipFuncSetAttribute failed", __func__);
+    return PFPP_EHIP;
   }
   hipLaunchKernelGGL(vattn_bwd_kernel, dim3((unsigned)(B * H)), dim3(VA_THREADS), lds, pfpp::as_stream(stream), qkv, out, dout, lse,
                      dqkv, key_valid, (int)E, (int)H, scale, pfpp_drop_thresh(p), 1.0f / (1.0f - p), seed, site);

@@ -126,13 +126,9 @@ extern "C" int pfpp_vq_encode(const float* z_e, const float* codebook, const int
   const int64_t total = F * rows_per_frag;
   if (total == 0) return PFPP_OK;
   const size_t smem = (size_t)n_codes * (VQ_DIM + 1) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_encode_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 2048 * (VQ_DIM + 1) * 4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_encode_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 2048 * (VQ_DIM + 1) * 4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_encode_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 2048 * (VQ_DIM + 1) * 4);
-    attr_set = true;
-  }
+  (void)pfpp_allow_dyn_lds<vq_encode_kernel<4>>(2048 * (VQ_DIM + 1) * 4);
+  (void)pfpp_allow_dyn_lds<vq_encode_kernel<16>>(2048 * (VQ_DIM + 1) * 4);
+  (void)pfpp_allow_dyn_lds<vq_encode_kernel<64>>(2048 * (VQ_DIM + 1) * 4);
   hipStream_t st = pfpp::as_stream(stream);
   // lanes per sub-vector: enough of them that the launch fills the chip (the argmin is the first minimum for every choice)
   if (total <= 2048)

@@ -26,7 +26,7 @@ SOURCES = {
     "attention.hip": [],
     "edgefeat.hip": ["-ffp-contract=off"],
     "gemm.hip": [],
-    "gemm_pl.hip": ["-munsafe-fp-atomics"] + (["-DPFPP_PL_LAB"] if os.environ.get("PFPP_PL_LAB") else []),
+    "gemm_pl.hip": ["-munsafe-fp-atomics"],
     "sa_fused.hip": [],
     "sa_train.hip": ["-munsafe-fp-atomics"],
     "tlayer.hip": [],
@@ -87,7 +87,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     hipcc = _hipcc()
     objdir = CSRC / "build"
     objdir.mkdir(exist_ok=True)
-    headers = [INCLUDE / "pfpp.h", CSRC / "pfpp_common.h", CSRC / "gemm_common.h", CSRC / "sa_common.h"]
+    headers = [INCLUDE / "pfpp.h", CSRC / "pfpp_common.h", CSRC / "gemm_common.h", CSRC / "lds_asm.h", CSRC / "sa_common.h"]
     # the linked library newer than every source and header: nothing to do — also where the object files did not travel (the GPU box
     # gets libpfpp_hip.so but not csrc/build/, .gpurunignore): without this a test fixture there would recompile all 25 units
     if not force and not _stale(LIB_PATH, [CSRC / src for src in SOURCES] + headers):

@@ -300,37 +300,6 @@ def _split_workspace(device):
     return ws
 
 
-def gemm_kernel_name(M: int, N: int, act: str, pool: int, batch: int, w_kmajor: bool, f16x3: bool = False, K: int = 0,
-                     presplit: bool = False, a_presplit: bool = False, fused_bn: bool = False, a_aff: bool = False) -> str:
-    """the template instantiation pfpp_gemm dispatches to (mirror of the choice in csrc/gemm.hip with the
-    default environment) — used to attribute HIP-event timings to the kernel names rocprofv3 reports"""
-    wide = N > 64 or act == "geglu"
-    if f16x3 and not w_kmajor:
-        if a_presplit:
-            if M >= 8192 and N >= 1024 and pool == 0:
-                return "gemm_f16x3_apre_kernel<4, 2, 2, 4, false>"
-            if M >= 8192 and pool != 32:
-                return "gemm_f16x3_apre_kernel<2, 2, 4, 2, true>"
-            t128 = ((M + 127) // 128) * ((N + 127) // 128) * batch
-            if t128 < 1024 and act != "geglu" and pool == 0:
-                return "gemm_f16x3_apre_kernel<2, 1, 2, 2, true>"
-            return "gemm_f16x3_apre_kernel<2, 2, 2, 2, true>"
-        if presplit and wide and M >= 8192 and N >= 1024 and pool == 0:
-            return "gemm_f16x3_kernel<4, 2, true, 2, 4, false, false>"
-        if presplit and wide and M >= 8192 and pool != 32:
-            return f"gemm_f16x3_kernel<2, 2, true, 4, 2, true, {'true' if a_aff else 'false'}>"
-        tiles128 = ((M + 127) // 128) * ((N + 127) // 128) * batch
-        if presplit and not fused_bn and pool == 0 and ((M + 63) // 64) * ((N + 63) // 64) * batch <= 256:
-            return "gemm_f16x3_deep_kernel<1, 2, 2, 2, 4>" if act == "geglu" else "gemm_f16x3_deep_kernel<1, 1, 2, 2, 8>"
-        deep = not fused_bn and tiles128 < 2048
-        if presplit and wide and tiles128 < 1024 and act != "geglu" and pool == 0:
-            return f"gemm_f16x3_kernel<2, 1, true, 2, 2, {'true' if deep else 'false'}, false>"
-        if presplit and deep:
-            return f"gemm_f16x3_kernel<2, {2 if wide else 1}, true, 2, 2, true, false>"
-        return f"gemm_f16x3_kernel<2, {2 if wide else 1}, {'true' if presplit else 'false'}, 2, 2, false, false>"
-    return f"gemm_f32_mfma_kernel<2, {2 if wide else 1}, {'true' if w_kmajor else 'false'}>"
-
-
 def gemm(A: torch.Tensor, W, *, M: int, N: int, K: int, lda: int, ldw: Optional[int] = None,
          out: Optional[torch.Tensor] = None, ldc: Optional[int] = None,
          bias: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
@@ -455,11 +424,7 @@ def gemm(A: torch.Tensor, W, *, M: int, N: int, K: int, lda: int, ldw: Optional[
         e0.record()
         check(_lib.load().pfpp_gemm(C.byref(args), _stream()), "pfpp_gemm")
         e1.record()
-        pl_name = _lib.load().pfpp_last_gemm_kernel().decode()        # set when the call went to the plane kernel (gemm_pl.hip)
-        GEMM_TRACE.append((e0, e1, 2.0 * M * N * K * batch,
-                           pl_name or gemm_kernel_name(M, N, act, pool, batch, w_kmajor, f16x3, K, planes is not None, a_planes is not None,
-                                                       a_affine is not None or stats is not None or c_min is not None, a_affine is not None),
-                           (M, N, K, batch, act, pool)))
+        GEMM_TRACE.append((e0, e1, 2.0 * M * N * K * batch, _lib.load().pfpp_last_gemm_kernel().decode(), (M, N, K, batch, act, pool)))
         return out
     check(_lib.load().pfpp_gemm(C.byref(args), _stream()), "pfpp_gemm")
     return out

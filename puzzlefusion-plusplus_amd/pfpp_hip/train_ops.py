@@ -49,28 +49,11 @@ def gemm_grad(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, *, M: int, N:
         e0.record()
         check(_lib.load().pfpp_gemm_grad(C.byref(a), _stream()), "pfpp_gemm_grad")
         e1.record()
-        ops.GEMM_TRACE.append((e0, e1, 2.0 * M * N * K * batch, grad_kernel_name(M, N, batch, a_kmajor, w_kmajor, split_k, accumulate),
+        ops.GEMM_TRACE.append((e0, e1, 2.0 * M * N * K * batch, _lib.load().pfpp_last_gemm_kernel().decode(),
                                (M, N, K, batch, "grad", 0)))
         return out
     check(_lib.load().pfpp_gemm_grad(C.byref(a), _stream()), "pfpp_gemm_grad")
     return out
-
-
-def grad_kernel_name(M: int, N: int, batch: int, a_kmajor: bool, w_kmajor: bool, split_k: int, accumulate: bool) -> str:
-    """the gemm_grad_kernel instantiation csrc/gemm_grad.hip dispatches to (mirror of its tile choice)"""
-    def tiles(bm, bn):
-        return ((M + bm - 1) // bm) * ((N + bn - 1) // bn) * batch
-    bm, bn = 128, 64
-    if tiles(256, 128) >= 384:
-        bm, bn = 256, 128
-    elif tiles(128, 128) >= 256 or N > 64:
-        bm, bn = 128, 128
-    if (bm, bn) == (128, 128) and tiles(128, 128) < 192 and split_k == 1 and N <= 2048:
-        bn = 64
-    if (bm, bn) == (128, 128) and accumulate and tiles(128, 128) < 40:
-        bn = 64
-    cfg = {(256, 128): "2, 2, 4, 2", (128, 128): "2, 2, 2, 2", (128, 64): "2, 1, 2, 2"}[(bm, bn)]
-    return f"gemm_grad_kernel<{cfg}, {'true' if a_kmajor else 'false'}, {'true' if w_kmajor else 'false'}>"
 
 
 def dx_splits(M: int, K_in: int, N_out: int) -> bool:
@@ -137,7 +120,7 @@ def grad_weight_group(problems, *, g_scale: float = 1.0) -> None:
         e0.record()
         check(_lib.load().pfpp_gemm_grad_group(arr, n, _stream()), "pfpp_gemm_grad_group")
         e1.record()
-        ops.GEMM_TRACE.append((e0, e1, flops, "gemm_grad_group_kernel<2, 2, 2, 2, true, true>", (n, int(flops // 1e6), 0, 1, "grad_group", 0)))
+        ops.GEMM_TRACE.append((e0, e1, flops, _lib.load().pfpp_last_gemm_kernel().decode(), (n, int(flops // 1e6), 0, 1, "grad_group", 0)))
         return
     check(_lib.load().pfpp_gemm_grad_group(arr, n, _stream()), "pfpp_gemm_grad_group")
 

@@ -39,7 +39,7 @@ def run(a_op, label):
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / iters
-    kern = _lib.load().pfpp_last_gemm_kernel().decode() or "register-staged kernel (csrc/gemm.hip)"
+    kern = _lib.load().pfpp_last_gemm_kernel().decode()
     tf = 2.0 * M * N * K / (ms * 1e-3) / 1e12
     print(f"M{M} N{N} K{K} {mode} {act} A={label}: {ms * 1e3:.1f} us  {tf:.1f} TFLOP/s algorithmic"
           + (f" = {tf / (2500.0 / 3.0):.3f} of the f16 dense peak / 3" if mode == "f16x3" else "") + f"   [{kern}]")

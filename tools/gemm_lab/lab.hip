@@ -1,6 +1,6 @@
 // Developer bench for the split-f16 GEMM kernels, through the C ABI of libpfpp_hip.so (no Python: a fresh GPU box
 // spends minutes importing torch).  For every shape: the default kernel (fp32 A, pre-split W) is the reference;
-// every plane variant (PFPP_GEMM_PL=1..3, and the register-staged pre-split kernel = 0) is compared with it bit for
+// the plane kernel's tiles (pfpp_gemm_planes variant 0 = the library's choice, 1, 2, 3, 6, 11) are compared with it bit for
 // bit and timed with HIP events.
 //   usage: lab [iters] M,N,K[,act] ...      act: 0 none, 3 gelu, r = residual + bias
 #include <hip/hip_runtime.h>
@@ -32,13 +32,17 @@ static float frand() {
 
 struct Shape { int64_t M, N, K; int act; bool res; };
 
-static float time_gemm(const pfpp_gemm_args& a, int iters, hipStream_t st) {
+static int run(const pfpp_gemm_args& a, hipStream_t st) { return pfpp_gemm(&a, (pfpp_stream_t)st); }
+static int run(const pfpp_gemm_planes_args& a, hipStream_t st) { return pfpp_gemm_planes(&a, (pfpp_stream_t)st); }
+
+template <class Args>
+static float time_gemm(const Args& a, int iters, hipStream_t st) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  for (int i = 0; i < 3; ++i) { int rc = pfpp_gemm(&a, (pfpp_stream_t)st); if (rc) { printf("pfpp_gemm rc %d: %s\n", rc, pfpp_last_error()); return -1.f; } }
+  for (int i = 0; i < 3; ++i) { int rc = run(a, st); if (rc) { printf("GEMM rc %d: %s\n", rc, pfpp_last_error()); return -1.f; } }
   CK(hipStreamSynchronize(st));
   CK(hipEventRecord(e0, st));
-  for (int i = 0; i < iters; ++i) pfpp_gemm(&a, (pfpp_stream_t)st);
+  for (int i = 0; i < iters; ++i) run(a, st);
   CK(hipEventRecord(e1, st));
   CK(hipEventSynchronize(e1));
   float ms = 0.f;
@@ -88,20 +92,21 @@ int main(int argc, char** argv) {
     a.act = s.act; a.batch = 1; a.zdiv = 1; a.precision = PFPP_GEMM_F16X3; a.alpha = 1.0f;
     if (s.res) a.residual = dR;
     const double gflop = 2.0 * M * N * K * 1e-9;
-    setenv("PFPP_GEMM_PL", "0", 1);
     float t_ref = time_gemm(a, iters, st);
     printf("M%-7ld N%-5ld K%-5ld act%d%s | default(fp32 A) %8.1f us %7.1f TF/s\n", M, N, K, s.act, s.res ? "+res" : "", t_ref, gflop / t_ref * 1e3);
     std::vector<float> c0((size_t)M * N), c1((size_t)M * N);
     CK(hipMemcpy(c0.data(), dC0, c0.size() * 4, hipMemcpyDeviceToHost));
-    a.A = nullptr; a.a_hi = ah; a.a_lo = al; a.C = dC1;
-    const char* only = getenv("LAB_VARIANTS");      // e.g. "13": variants 1 and 3 only; letters a.. = 10..
-    for (int v = 0; v <= 12; ++v) {
+    pfpp_gemm_planes_args q;
+    memset(&q, 0, sizeof(q));
+    q.a_hi = ah; q.a_lo = al; q.w_hi = wh; q.w_lo = wl; q.C = dC1; q.bias = db; q.residual = a.residual;
+    q.M = M; q.N = N; q.K = K; q.lda = K; q.ldw = K; q.ldc = N; q.ldr = N;
+    q.act = s.act; q.splits = 1; q.alpha = 1.0f;
+    const char* only = getenv("LAB_VARIANTS");      // e.g. "13": variants 1 and 3 only; b = 11
+    for (int v : {0, 1, 2, 3, 6, 11}) {
       if (only && !strchr(only, v < 10 ? '0' + v : 'a' + v - 10)) continue;
-      char buf[8];
-      snprintf(buf, sizeof buf, "%d", v);
-      setenv("PFPP_GEMM_PL", buf, 1);
+      q.variant = v;
       CK(hipMemsetAsync(dC1, 0xFF, (size_t)M * N * 4, st));
-      float t = time_gemm(a, iters, st);
+      float t = time_gemm(q, iters, st);
       CK(hipMemcpy(c1.data(), dC1, c1.size() * 4, hipMemcpyDeviceToHost));
       size_t bad = 0; double maxd = 0.0; size_t first = (size_t)-1;
       for (size_t i = 0; i < c0.size(); ++i) {
