@@ -45,8 +45,9 @@ struct GemmP {
   int reserved;   // always 0 (once a mask of lab ablation switches): kept so that the layout, and with it every kernel's argument offsets, stays as it was
 };
 
-// template instantiation (and "+pl_reduce_kernel" where a slab reduction follows) of the most recent GEMM launch of this
-// thread: written by every launcher of gemm.hip, gemm_pl.hip and gemm_grad.hip, read by pfpp_last_gemm_kernel (gemm_pl.hip)
+// template instantiation (and "+pl_reduce_kernel" where a slab reduction follows) of the most recent GEMM or set-abstraction
+// stage launch of this thread, as a kernel trace prints it: written by every launcher of gemm.hip, gemm_pl.hip, gemm_grad.hip and
+// pfpp_sa_train_stage (sa_train.hip), read by pfpp_last_gemm_kernel (gemm_pl.hip)
 namespace pl { extern thread_local char last_kernel[96]; }
 // A launcher formats the name of its instantiation once (a function-local static) and copies it per launch: no printf on the
 // launch path.  80 characters + the longest suffix (17) fit last_kernel.

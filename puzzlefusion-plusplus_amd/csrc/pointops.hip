@@ -124,8 +124,9 @@ __device__ __forceinline__ float wave_max_f32(float v) {
 // ---------------------------------------------------------------------------
 // One step of the farthest-point chain, shared by fps_kernel and the fused sampling kernel.  The step is a dependent chain (centroid
 // -> distances -> argmax -> next centroid), 255 of them for level 1: what counts is its LATENCY.
-//   * distances two points at a time (v_pk_add_f32 / v_pk_mul_f32: the same correctly rounded sub, mul, add per element, in the
-//     reference's order ((dx^2 + dy^2) + dz^2); -ffp-contract=off keeps them apart);
+//   * distances written two points at a time (2-vectors: the same correctly rounded sub, mul, add per element, in the reference's
+//     order ((dx^2 + dy^2) + dz^2); -ffp-contract=off keeps them apart).  The library is built with the packed fp32 operations off
+//     (pfpp_hip/build.py NO_PK), so the shipped code holds scalar v_sub / v_mul / v_add per element, no v_pk_add_f32 / v_pk_mul_f32;
 //   * the lane's best is a max tree over its running minima (v_max3_f32), the index is NOT carried through the loop: after the wave
 //     maximum, the lowest lane holding it is found by ballot (blocked ownership: lowest lane = lowest index block) and the first of its
 //     points equal to the maximum by PPT compares — torch.argmax's first-maximum rule, as before;

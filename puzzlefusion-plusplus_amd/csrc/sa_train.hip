@@ -20,15 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_common.h"
 #include "pfpp.h"
 #include "pfpp_common.h"
 #include "sa_common.h"
-
-// lab only (tools/lab/sa_ablate.sh): what the rows kernels' time is made of.  1 = no matrix instructions, 2 = no normalise / split of the
-// operand rows, 4 = no statistics / stores, 8 = the row loads of the first half only
-#ifndef SA_ABL
-#define SA_ABL 0
-#endif
 
 namespace {
 
@@ -538,120 +533,13 @@ __global__ __launch_bounds__(256, 1) void sa2_train_kernel(const SaTP p) {
 // relu(fma(y_2, a_mul, a_add)) -> third convolution -> sums of y_3 + per-neighbourhood max / min.  The layer-wise form of this is
 // the fp32-A plane GEMM (one workgroup per 128 x 128 tile: 2 column tiles re-read and re-convert every A element, a DMA ring
 // prologue + epilogue per 4-K-tile contraction: 505 us).  Here the 256 x 128 weight planes stay in LDS for the lifetime of one
-// persistent workgroup per CU; a wave owns a neighbourhood's 64 rows: every lane fetches the 32-byte runs of ITS row, normalises
-// and splits them once, and keeps the fragments in registers for all 8 column tiles.
-template <int K, int N>
-__global__ __launch_bounds__(256, 1) void sa_rows_train_kernel(const SaTP p) {
-  constexpr int LD = K + 8;
-  extern __shared__ __align__(16) unsigned char sar_smem[];
-  _Float16* Wh = reinterpret_cast<_Float16*>(sar_smem);
-  _Float16* Wl = Wh + N * LD;
-  float* M = reinterpret_cast<float*>(Wl + N * LD);
-  float* A = M + K;
-  const int tid = threadIdx.x;
-  for (int i = tid; i < N * (K / 8); i += 256) {
-    const int r = i / (K / 8), c8 = i - r * (K / 8);
-    *reinterpret_cast<uint4*>(Wh + r * LD + c8 * 8) = *reinterpret_cast<const uint4*>(p.wh[2] + (size_t)r * K + c8 * 8);
-    *reinterpret_cast<uint4*>(Wl + r * LD + c8 * 8) = *reinterpret_cast<const uint4*>(p.wl[2] + (size_t)r * K + c8 * 8);
-  }
-  for (int i = tid; i < K; i += 256) { M[i] = p.am[1][i]; A[i] = p.aa[1][i]; }
-  __syncthreads();
-
-  const int lane = tid & 63, wave = tid >> 6;
-  const int l31 = lane & 31, lhi = lane >> 5;
-  float bs[N / 32];
-  double ss[N / 32], sq[N / 32];
-#pragma unroll
-  for (int n = 0; n < N / 32; ++n) { bs[n] = p.bias[2][n * 32 + l31]; ss[n] = 0.0; sq[n] = 0.0; }
-
-  const int stride = gridDim.x * 4;
-  const int g0 = blockIdx.x * 4 + wave;
-  const float* rows = p.y_out;
-  auto load_rows = [&](int g, float4 (&raw)[2][K / 16][2]) {
-    const int gc = g < p.G ? g : p.G - 1;
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      const float* row = rows + ((int64_t)gc * 64 + st * 32 + l31) * K + lhi * 8;
-#pragma unroll
-      for (int ks = 0; ks < K / 16; ++ks) {
-        raw[st][ks][0] = *reinterpret_cast<const float4*>(row + ks * 16);
-        raw[st][ks][1] = *reinterpret_cast<const float4*>(row + ks * 16 + 4);
-      }
-    }
-  };
-  float4 raw[2][K / 16][2];
-  load_rows(g0, raw);
-
-  for (int g = g0; g < p.G; g += stride) {
-    asm volatile("" ::: "memory");
-    half8 fh[K / 16][2], fl[K / 16][2];
-#pragma unroll
-    for (int ks = 0; ks < K / 16; ++ks) {
-      const float4 m0 = *reinterpret_cast<const float4*>(M + ks * 16 + lhi * 8), m1 = *reinterpret_cast<const float4*>(M + ks * 16 + lhi * 8 + 4);
-      const float4 a0 = *reinterpret_cast<const float4*>(A + ks * 16 + lhi * 8), a1 = *reinterpret_cast<const float4*>(A + ks * 16 + lhi * 8 + 4);
-      const float mv[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w}, av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const float4 r0 = raw[st][ks][0], r1 = raw[st][ks][1];
-        const float x[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const float v = fmaxf(__builtin_fmaf(x[q], mv[q], av[q]), 0.0f);     // relu(batch-norm(y_2)), as the GEMM's A loader
-          _Float16 h, l;
-          split1(v, h, l);
-          fh[ks][st][q] = h; fl[ks][st][q] = l;
-        }
-      }
-    }
-    load_rows(g + stride, raw);          // the next neighbourhood's rows are in flight during this one's contraction
-    // the column-tile loop stays rolled: unrolled, the compiler overlaps the tiles' accumulators and weight fragments and spills
-    // 150 registers
-#pragma unroll 1
-    for (int n = 0; n < N / 32; ++n) {
-      f32x16 acc[2];
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[st][e] = 0.0f;
-#pragma unroll
-      for (int ks = 0; ks < K / 16; ++ks) {
-        const half8 wh = *reinterpret_cast<const half8*>(Wh + (n * 32 + l31) * LD + ks * 16 + lhi * 8);
-        const half8 wl = *reinterpret_cast<const half8*>(Wl + (n * 32 + l31) * LD + ks * 16 + lhi * 8);
-#pragma unroll
-        for (int st = 0; st < 2; ++st) acc[st] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl[ks][st], wh, acc[st], 0, 0, 0);
-#pragma unroll
-        for (int st = 0; st < 2; ++st) acc[st] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[ks][st], wl, acc[st], 0, 0, 0);
-#pragma unroll
-        for (int st = 0; st < 2; ++st) acc[st] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[ks][st], wh, acc[st], 0, 0, 0);
-      }
-      float s = 0.0f, q = 0.0f, mx = -__builtin_huge_valf(), mn = __builtin_huge_valf();
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const float y = acc[st][e] + bs[n];
-          s += y;
-          q = __builtin_fmaf(y, y, q);
-          mx = fmaxf(mx, y); mn = fminf(mn, y);
-        }
-      ss[n] += (double)s;
-      sq[n] += (double)q;
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      mn = fminf(mn, __shfl_xor(mn, 32));
-      if (lhi == 0) {
-        p.out_max[(int64_t)g * N + n * 32 + l31] = mx;
-        p.out_min[(int64_t)g * N + n * 32 + l31] = mn;
-      }
-    }
-  }
-#pragma unroll
-  for (int n = 0; n < N / 32; ++n) flush_stats(p.stats, p.copies, N, n * 32 + l31, lhi, ss[n], sq[n]);
-}
-
-// The same stage with EIGHT waves per workgroup, two per SIMD: a wave takes half a neighbourhood (32 rows) at a time, so its raw rows,
-// operand fragments and one accumulator tile fit in 256 registers and the split / statistics arithmetic of one wave runs under the
-// matrix instructions of the other wave of its SIMD (with one wave per SIMD they alternate: 37 % of the matrix peak).  The weight
-// fragments are read from LDS once per 32 rows instead of once per 64; the neighbourhood's max / min are carried across its two halves.
+// persistent workgroup per CU; every lane fetches the 32-byte runs of ITS row, normalises and splits them once, and keeps the
+// fragments in registers for all 8 column tiles.
+// EIGHT waves per workgroup, two per SIMD: a wave takes half a neighbourhood (32 rows) at a time, so its raw rows, operand fragments
+// and one accumulator tile fit in 256 registers and the split / statistics arithmetic of one wave runs under the matrix instructions
+// of the other wave of its SIMD (a 4-wave form with a whole neighbourhood per wave, one wave per SIMD, alternated the two: 37 % of
+// the matrix peak).  The weight fragments are read from LDS once per 32 rows; the neighbourhood's max / min are carried across its
+// two halves.
 template <int K, int N>
 __global__ __launch_bounds__(512, 1) void sa_rows8_train_kernel(const SaTP p) {
   constexpr int LD = K + 8;
@@ -715,7 +603,6 @@ __global__ __launch_bounds__(512, 1) void sa_rows8_train_kernel(const SaTP p) {
         const float x[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          if (SA_ABL & 2) { fh[ks][q] = (_Float16)x[q]; fl[ks][q] = (_Float16)mv[q]; continue; }
           const float v = fmaxf(__builtin_fmaf(x[q], mv[q], av[q]), 0.0f);     // relu(batch-norm(y_2)), as the GEMM's A loader
           _Float16 hh, ll;
           split1(v, hh, ll);
@@ -723,10 +610,8 @@ __global__ __launch_bounds__(512, 1) void sa_rows8_train_kernel(const SaTP p) {
         }
       }
       // the next half's rows are in flight during this one's contraction
-      if (!(SA_ABL & 8)) {
-        if (h + 1 < nh) load_rows(g, 1, c, raw);
-        else load_rows(g1, 0, c1, raw);
-      }
+      if (h + 1 < nh) load_rows(g, 1, c, raw);
+      else load_rows(g1, 0, c1, raw);
 #pragma unroll 1
       for (int n = 0; n < N / 32; ++n) {
         f32x16 acc;
@@ -736,12 +621,10 @@ __global__ __launch_bounds__(512, 1) void sa_rows8_train_kernel(const SaTP p) {
         for (int ks = 0; ks < K / 16; ++ks) {
           const half8 wh = *reinterpret_cast<const half8*>(Wh + (n * 32 + l31) * LD + ks * 16 + lhi * 8);
           const half8 wl = *reinterpret_cast<const half8*>(Wl + (n * 32 + l31) * LD + ks * 16 + lhi * 8);
-          if (SA_ABL & 1) { asm volatile("" :: "v"(fl[ks]), "v"(fh[ks]), "v"(wh), "v"(wl)); continue; }
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl[ks], wh, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[ks], wl, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[ks], wh, acc, 0, 0, 0);
         }
-        if (SA_ABL & 4) { asm volatile("" :: "v"(acc)); continue; }
         float s = 0.0f, q = 0.0f, hi = -__builtin_huge_valf(), lo = __builtin_huge_valf();
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -937,12 +820,6 @@ __global__ __launch_bounds__(256, 1) void sa_wide_train_kernel(const SaTP p, con
           fh[ks][q8] = h; fl[ks][q8] = l;
         }
       }
-      if (SA_ABL & 2) {
-#pragma unroll
-        for (int ks = 0; ks < K / 16; ++ks)
-#pragma unroll
-          for (int q8 = 0; q8 < 8; ++q8) { fh[ks][q8] = (_Float16)reinterpret_cast<const float*>(&raw[ks][0])[q8]; fl[ks][q8] = fh[ks][q8]; }
-      }
       if (GATHER) {
 #pragma unroll
         for (int q8 = 0; q8 < 8; ++q8) { fh[KS - 1][q8] = (_Float16)0.0f; fl[KS - 1][q8] = (_Float16)0.0f; }
@@ -956,7 +833,7 @@ __global__ __launch_bounds__(256, 1) void sa_wide_train_kernel(const SaTP p, con
         }
       }
       // the rows of the next half (or of the next neighbourhood) travel during this half's contraction
-      if (!(SA_ABL & 8)) { if (half + 1 < nh) load_half(g, 1, lv, raw, qx, cx); else load_half(g1, 0, lv1, raw, qx, cx); }
+      if (half + 1 < nh) load_half(g, 1, lv, raw, qx, cx); else load_half(g1, 0, lv1, raw, qx, cx);
       f32x16 acc[4];
 #pragma unroll
       for (int n = 0; n < 4; ++n)
@@ -970,7 +847,6 @@ __global__ __launch_bounds__(256, 1) void sa_wide_train_kernel(const SaTP p, con
           wh[n] = *reinterpret_cast<const half8*>(Wh + (n * 32 + l31) * LD + ks * 16 + lhi * 8);
           wl[n] = *reinterpret_cast<const half8*>(Wl + (n * 32 + l31) * LD + ks * 16 + lhi * 8);
         }
-        if (SA_ABL & 1) { asm volatile("" :: "v"(fl[ks]), "v"(fh[ks]), "v"(wh[0]), "v"(wl[0]), "v"(wh[1]), "v"(wl[1]), "v"(wh[2]), "v"(wl[2]), "v"(wh[3]), "v"(wl[3])); continue; }
         // term-major: consecutive MFMAs on different accumulators (the three products of one accumulator keep their order)
 #pragma unroll
         for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl[ks], wh[n], acc[n], 0, 0, 0);
@@ -979,7 +855,6 @@ __global__ __launch_bounds__(256, 1) void sa_wide_train_kernel(const SaTP p, con
 #pragma unroll
         for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[ks], wh[n], acc[n], 0, 0, 0);
       }
-      if (SA_ABL & 4) { asm volatile("" :: "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3])); continue; }
       if (EVAL) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
@@ -1251,152 +1126,160 @@ extern "C" int pfpp_sa_pad_schedule(const int32_t* idx, int64_t G, int64_t ns, i
   return pfpp::check_launch("pfpp_sa_pad_schedule");
 }
 
+namespace {
+
+using pfpp_gemm_detail::KernelName;
+using pfpp_gemm_detail::report_kernel;
+
+// the three level shapes of the path: no input features (3 -> 64 -> 64 -> 128, 32 neighbours: stage k recomputes layers 1..k-1),
+// 128 features (-> 128 -> 128 -> 256, 64 neighbours: stages 1 / 2 recompute, stage 3 reads the raw second-layer rows) and 256 features
+// (-> 256 -> 256 -> 512, 64 neighbours: one rows launch per layer)
+enum class SaLevel { NoFeatures, Feats128, Feats256 };
+
+// one enumerator per launch statement of pfpp_sa_train_stage
+enum class SaKern {
+  Sa1Stage1, Sa1Stage2, Sa1Stage3, Sa2Stage1, Sa2Stage2, Rows8, FirstStats128, FirstStats256, Table128, Table256, Wide1, Wide2, Wide3
+};
+
+// The kernel of a stage: a function of the level, the stage and whether the first layer comes from the per-point table (u_in at stages
+// 1 and 2 of a level with D = 128 or 256 features), never of the sizes.  tests/test_gpu_parity.py pins every enumerator.
+SaKern choose_sa_stage(int D, int stage, bool table, SaLevel level) {
+  if (table) return stage == 1 ? (D == 128 ? SaKern::FirstStats128 : SaKern::FirstStats256) : (D == 128 ? SaKern::Table128 : SaKern::Table256);
+  switch (level) {
+    case SaLevel::NoFeatures: return stage == 1 ? SaKern::Sa1Stage1 : stage == 2 ? SaKern::Sa1Stage2 : SaKern::Sa1Stage3;
+    case SaLevel::Feats256: return stage == 1 ? SaKern::Wide1 : stage == 2 ? SaKern::Wide2 : SaKern::Wide3;
+    case SaLevel::Feats128: break;
+  }
+  return stage == 1 ? SaKern::Sa2Stage1 : stage == 2 ? SaKern::Sa2Stage2 : SaKern::Rows8;
+}
+
+SaTP fill_sa(const pfpp_sa_train_args* a, bool table) {
+  SaTP p;
+  p.xyz = a->xyz; p.ctr = a->new_xyz; p.feats = a->feats; p.idx = a->idx;
+  for (int i = 0; i < 3; ++i) { p.wh[i] = (const _Float16*)a->w_hi[i]; p.wl[i] = (const _Float16*)a->w_lo[i]; p.bias[i] = a->bias[i]; }
+  for (int i = 0; i < 2; ++i) { p.am[i] = a->a_mul[i]; p.aa[i] = a->a_add[i]; }
+  p.stats = a->stats; p.copies = (int)a->stats_copies;
+  p.y_out = a->y_out; p.out_max = a->out_max; p.out_min = a->out_min;
+  p.N = (int)a->N; p.S = (int)a->S; p.G = (int)(a->F * a->S);
+  p.u = table ? a->u_in : nullptr; p.D = (int)a->D;
+  p.e_hi = nullptr; p.e_lo = nullptr; p.sched = a->sched;
+  return p;
+}
+
+// persistent launch whose workgroup takes `per` neighbourhoods a round: `cap` workgroups, fewer where there is less work
+unsigned persistent_grid(int G, int per, int64_t cap) {
+  const int64_t need = (G + per - 1) / per;
+  return (unsigned)(need < cap ? need : cap);
+}
+
+// rows launch over n_total output columns in 128-column slices: a whole number of 8-workgroup rounds per slice, so that the slices of
+// a row group share an XCD
+unsigned rows_grid(int64_t cap, int n_total) {
+  const int n_slices = n_total / 128;
+  cap = cap / (8 * n_slices) * (8 * n_slices);
+  return (unsigned)(cap < n_slices ? n_slices : cap);
+}
+
+// LDS bytes of the hi and lo planes of a [rows, k] weight slice (rows padded by 8 halfs) + n_vec fp32 vectors of k entries
+constexpr size_t sa_lds(int rows, int k, int n_vec) { return (size_t)2 * rows * (k + 8) * sizeof(_Float16) + (size_t)n_vec * k * sizeof(float); }
+constexpr int gathered(int d) { return (d / 16 + 1) * 16; }      // [feats | xyz | 0]: one more 16-deep step than the features
+
+// `instantiation` = the name a kernel trace prints for KERN: what pfpp_last_gemm_kernel() reports for this launch
+template <auto KERN, typename... Args>
+int launch_sa(const char* instantiation, unsigned grid, unsigned block, size_t smem, hipStream_t st, Args... args) {
+  static const KernelName name("%s", instantiation);
+  report_kernel(name);
+  if (smem) (void)pfpp_allow_dyn_lds<KERN>((int)smem);
+  hipLaunchKernelGGL(KERN, dim3(grid), dim3(block), smem, st, args...);
+  return pfpp::check_launch("pfpp_sa_train_stage");
+}
+
+}  // namespace
+
 extern "C" int pfpp_sa_train_stage(const pfpp_sa_train_args* a, pfpp_stream_t stream) {
+  pfpp_gemm_detail::pl::last_kernel[0] = 0;      // a call that launches nothing (F == 0, rejected arguments) reports ""
   PFPP_REQUIRE(a, "null args");
   PFPP_REQUIRE(a->xyz && a->new_xyz && a->idx && a->stats, "null pointer");
   PFPP_REQUIRE(a->F >= 0 && a->N > 0 && a->S > 0 && a->stats_copies >= 1, "bad sizes");
-  const bool lvl1 = a->feats == nullptr;
   PFPP_REQUIRE(a->stage >= 1 && a->stage <= 3, "stage out of range (1..3)");
-  if (a->u_in && a->stage <= 2) {
-    // first layer by linearity: stage 1 = statistics of U[idx] - W1_xyz . centroid, stage 2 = second layer from the gathered rows
+  const int L = a->stage;
+  const bool lvl1 = a->feats == nullptr;
+  // first layer by linearity: stage 1 = statistics of U[idx] - W1_xyz . centroid, stage 2 = second layer from the gathered rows
+  const bool table = a->u_in && L <= 2;
+  const SaLevel level = lvl1 ? SaLevel::NoFeatures : a->D == 256 ? SaLevel::Feats256 : SaLevel::Feats128;
+  if (table) {
     PFPP_REQUIRE(!lvl1, "the per-point table belongs to a level with input features");
     PFPP_SUPPORTED(a->ns == 64 && ((a->D == 128 && a->C1 == 128 && a->C2 == 128) || (a->D == 256 && a->C1 == 256 && a->C2 == 256)),
                    "per-point first layer: nsample 64, (128 -> 128 -> 128) or (256 -> 256 -> 256) only");
     PFPP_REQUIRE(a->w_hi[0] && a->w_lo[0] && pfpp::aligned16(a->u_in), "first-layer planes / table alignment");
     PFPP_REQUIRE(a->F * a->S < (1ll << 25), "too many neighbourhoods");
-    if (a->F == 0) return PFPP_OK;
-    SaTP p;
-    p.xyz = a->xyz; p.ctr = a->new_xyz; p.feats = a->feats; p.idx = a->idx;
-    for (int i = 0; i < 3; ++i) { p.wh[i] = (const _Float16*)a->w_hi[i]; p.wl[i] = (const _Float16*)a->w_lo[i]; p.bias[i] = a->bias[i]; }
-    for (int i = 0; i < 2; ++i) { p.am[i] = a->a_mul[i]; p.aa[i] = a->a_add[i]; }
-    p.stats = a->stats; p.copies = (int)a->stats_copies;
-    p.y_out = a->y_out; p.out_max = a->out_max; p.out_min = a->out_min;
-    p.N = (int)a->N; p.S = (int)a->S; p.G = (int)(a->F * a->S);
-    p.u = a->u_in; p.D = (int)a->D;
-    p.e_hi = nullptr; p.e_lo = nullptr; p.sched = a->sched;
-    hipStream_t st = pfpp::as_stream(stream);
-    int64_t cap = a->max_workgroups > 0 ? a->max_workgroups : 256;
-    if (a->stage == 1) {
-      const int64_t need = (p.G + 3) / 4;
-      const unsigned grid = (unsigned)(need < 4 * cap ? need : 4 * cap);          // light workgroups: four per CU
-      if (a->D == 128) hipLaunchKernelGGL((sa_first_stats_kernel<128>), dim3(grid), dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((sa_first_stats_kernel<256>), dim3(grid), dim3(256), 0, st, p);
-      return pfpp::check_launch("pfpp_sa_train_stage");
-    }
-    PFPP_REQUIRE(a->w_hi[1] && a->w_lo[1] && a->bias[1] && pfpp::aligned16(a->w_hi[1]) && pfpp::aligned16(a->w_lo[1]) && a->a_mul[0] &&
-                 a->a_add[0] && a->y_out && pfpp::aligned16(a->y_out), "second-layer operands / first-layer affine / y_out missing");
-    const int n_total = (int)a->C2;
-    const int n_slices = n_total / 128;
-    cap = cap / (8 * n_slices) * (8 * n_slices);
-    if (cap < n_slices) cap = n_slices;
-    constexpr size_t smem_128 = (size_t)2 * 128 * (128 + 8) * sizeof(_Float16) + (2 + 4 + 3) * 128 * sizeof(float);
-    constexpr size_t smem_256 = (size_t)2 * 128 * (256 + 8) * sizeof(_Float16) + (2 + 4 + 3) * 256 * sizeof(float);
-    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<128, 2, true>>((int)smem_128);
-    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<256, 2, true>>((int)smem_256);
-    if (a->D == 128) hipLaunchKernelGGL((sa_wide_train_kernel<128, 2, true>), dim3((unsigned)cap), dim3(256), smem_128, st, p, (const float*)nullptr, n_total);
-    else hipLaunchKernelGGL((sa_wide_train_kernel<256, 2, true>), dim3((unsigned)cap), dim3(256), smem_256, st, p, (const float*)nullptr, n_total);
-    return pfpp::check_launch("pfpp_sa_train_stage");
-  }
-  if (!lvl1 && a->D == 256) {
-    // wide level (sa3): one rows launch per layer, the [rows, 256] pre-activations in between
+    PFPP_REQUIRE(L == 1 || (a->w_hi[1] && a->w_lo[1] && a->bias[1] && pfpp::aligned16(a->w_hi[1]) && pfpp::aligned16(a->w_lo[1]) && a->a_mul[0] &&
+                            a->a_add[0] && a->y_out && pfpp::aligned16(a->y_out)), "second-layer operands / first-layer affine / y_out missing");
+  } else if (level == SaLevel::Feats256) {
     PFPP_SUPPORTED(a->ns == 64 && a->C1 == 256 && a->C2 == 256 && a->C3 == 512, "wide train-mode level: nsample 64, 256 features, widths 256/256/512 only");
-    const int L = a->stage;
     PFPP_REQUIRE(a->w_hi[L - 1] && a->w_lo[L - 1] && a->bias[L - 1] && pfpp::aligned16(a->w_hi[L - 1]) && pfpp::aligned16(a->w_lo[L - 1]),
                  "weights / bias of the layer this stage computes are missing");
     PFPP_REQUIRE(L == 1 || (a->a_mul[L - 2] && a->a_add[L - 2] && a->y_in && pfpp::aligned16(a->y_in)), "the previous layer's rows / affine are missing");
     PFPP_REQUIRE(L == 3 ? (a->out_max && a->out_min) : (a->y_out != nullptr), "output missing");
     PFPP_REQUIRE(pfpp::aligned16(a->feats) && a->F * a->S < (1ll << 25), "alignment / too many neighbourhoods");
-    if (a->F == 0) return PFPP_OK;
-    SaTP p;
-    p.xyz = a->xyz; p.ctr = a->new_xyz; p.feats = a->feats; p.idx = a->idx;
-    for (int i = 0; i < 3; ++i) { p.wh[i] = (const _Float16*)a->w_hi[i]; p.wl[i] = (const _Float16*)a->w_lo[i]; p.bias[i] = a->bias[i]; }
-    for (int i = 0; i < 2; ++i) { p.am[i] = a->a_mul[i]; p.aa[i] = a->a_add[i]; }
-    p.stats = a->stats; p.copies = (int)a->stats_copies;
-    p.y_out = a->y_out; p.out_max = a->out_max; p.out_min = a->out_min;
-    p.N = (int)a->N; p.S = (int)a->S; p.G = (int)(a->F * a->S);
-    p.u = nullptr; p.D = (int)a->D;
-    p.e_hi = nullptr; p.e_lo = nullptr; p.sched = a->sched;
     PFPP_SUPPORTED(!(a->sched && L == 1), "the grouped first layer of the wide level takes no padding schedule (use the per-point table: u_in)");
-    const int n_total = L == 3 ? 512 : 256;
-    const int n_slices = n_total / 128;
-    int64_t cap = a->max_workgroups > 0 ? a->max_workgroups : 256;
-    cap = cap / (8 * n_slices) * (8 * n_slices);           // a whole number of 8-workgroup rounds per column slice: the slices of a row group share an XCD
-    if (cap < n_slices) cap = n_slices;
-    const unsigned grid = (unsigned)cap;
-    constexpr size_t smem_g = (size_t)2 * 128 * ((256 / 16 + 1) * 16 + 8) * sizeof(_Float16) + 2 * 256 * sizeof(float);
-    constexpr size_t smem_r = (size_t)2 * 128 * (256 + 8) * sizeof(_Float16) + 2 * 256 * sizeof(float);
-    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<256, 1>>((int)smem_g);
-    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<256, 2>>((int)smem_r);
-    (void)pfpp_allow_dyn_lds<sa_wide_train_kernel<256, 3>>((int)smem_r);
-    hipStream_t st = pfpp::as_stream(stream);
-    if (L == 1) hipLaunchKernelGGL((sa_wide_train_kernel<256, 1>), dim3(grid), dim3(256), smem_g, st, p, a->y_in, n_total);
-    else if (L == 2) hipLaunchKernelGGL((sa_wide_train_kernel<256, 2>), dim3(grid), dim3(256), smem_r, st, p, a->y_in, n_total);
-    else hipLaunchKernelGGL((sa_wide_train_kernel<256, 3>), dim3(grid), dim3(256), smem_r, st, p, a->y_in, n_total);
-    return pfpp::check_launch("pfpp_sa_train_stage");
-  }
-  const bool rows3 = !lvl1 && a->stage == 3;          // reads the raw rows stage 2 wrote: only layer 3's operands are needed
-  for (int i = rows3 ? 2 : 0; i < a->stage; ++i) {
-    PFPP_REQUIRE(a->w_hi[i] && a->w_lo[i] && a->bias[i], "weights / bias of a layer this stage computes are missing");
-    PFPP_REQUIRE(pfpp::aligned16(a->w_hi[i]) && pfpp::aligned16(a->w_lo[i]), "planes must be 16-byte aligned");
-  }
-  for (int i = rows3 ? 1 : 0; i + 1 < a->stage; ++i)
-    PFPP_REQUIRE(a->a_mul[i] && a->a_add[i], "finalised BatchNorm affine of an earlier layer is missing");
-  if (lvl1) {
-    PFPP_SUPPORTED(!a->sched, "no padding schedule for the 32-neighbour level");
-    PFPP_SUPPORTED(a->ns == 32 && a->C1 == 64 && a->C2 == 64 && a->C3 == 128, "train-mode chain without features: nsample 32, widths 64/64/128 only");
-    PFPP_REQUIRE(a->stage < 3 || (a->out_max && a->out_min), "stage 3 writes the per-neighbourhood max and min");
-    PFPP_REQUIRE(a->F * a->S < (1ll << 31), "too many neighbourhoods");
   } else {
-    PFPP_SUPPORTED(a->ns == 64 && a->D == 128 && a->C1 == 128 && a->C2 == 128 && (a->stage < 3 || a->C3 == 256),
-                   "train-mode chain with features: nsample 64, 128 features, widths 128/128/256 only");
-    PFPP_REQUIRE(a->stage < 2 || (a->y_out && pfpp::aligned16(a->y_out)), "stage 2 writes / stage 3 reads the raw layer-2 rows");
-    PFPP_REQUIRE(a->stage < 3 || (a->out_max && a->out_min), "stage 3 writes the per-neighbourhood max and min");
-    PFPP_REQUIRE(pfpp::aligned16(a->feats), "16-byte alignment");
-    PFPP_REQUIRE(a->F * a->S < (1ll << 25), "too many neighbourhoods");
-  }
-  if (a->F == 0) return PFPP_OK;
-  SaTP p;
-  p.xyz = a->xyz; p.ctr = a->new_xyz; p.feats = a->feats; p.idx = a->idx;
-  for (int i = 0; i < 3; ++i) {
-    p.wh[i] = (const _Float16*)a->w_hi[i]; p.wl[i] = (const _Float16*)a->w_lo[i]; p.bias[i] = a->bias[i];
-  }
-  for (int i = 0; i < 2; ++i) { p.am[i] = a->a_mul[i]; p.aa[i] = a->a_add[i]; }
-  p.stats = a->stats; p.copies = (int)a->stats_copies;
-  p.y_out = a->y_out; p.out_max = a->out_max; p.out_min = a->out_min;
-  p.N = (int)a->N; p.S = (int)a->S; p.G = (int)(a->F * a->S);
-  p.u = nullptr; p.D = (int)a->D;
-  p.e_hi = nullptr; p.e_lo = nullptr; p.sched = a->sched;
-  const int64_t cap = a->max_workgroups > 0 ? a->max_workgroups : 256;       // persistent: one 4-wave workgroup per CU the stream may use
-  const int64_t wgs_needed = (p.G + 3) / 4;
-  const unsigned grid = (unsigned)(wgs_needed < cap ? wgs_needed : cap);
-  hipStream_t st = pfpp::as_stream(stream);
-  if (lvl1) {
-    if (a->stage == 1) hipLaunchKernelGGL((sa1_train_kernel<64, 64, 128, 1>), dim3(grid), dim3(256), 0, st, p);
-    else if (a->stage == 2) hipLaunchKernelGGL((sa1_train_kernel<64, 64, 128, 2>), dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((sa1_train_kernel<64, 64, 128, 3>), dim3(grid), dim3(256), 0, st, p);
-  } else {
-    constexpr int d = 128, c1 = 128, c2 = 128;
-    constexpr size_t smem1 = (size_t)2 * c1 * ((d / 16 + 1) * 16 + 8) * sizeof(_Float16);
-    constexpr size_t smem2 = smem1 + (size_t)2 * c2 * (c1 + 8) * sizeof(_Float16) + (size_t)3 * c1 * sizeof(float);
-    constexpr int c3 = 256;
-    constexpr size_t smem3 = (size_t)2 * c3 * (c2 + 8) * sizeof(_Float16) + (size_t)2 * c2 * sizeof(float);
-    (void)pfpp_allow_dyn_lds<sa_rows_train_kernel<c2, c3>>((int)smem3);
-    (void)pfpp_allow_dyn_lds<sa_rows8_train_kernel<c2, c3>>((int)smem3);
-    (void)pfpp_allow_dyn_lds<sa2_train_kernel<d, c1, c2, 1>>((int)smem1);
-    (void)pfpp_allow_dyn_lds<sa2_train_kernel<d, c1, c2, 2>>((int)smem2);
-    PFPP_SUPPORTED(!a->sched || a->stage == 3, "stages 1 and 2 take the padding schedule only in their table-fed form (u_in)");
-    if (a->stage == 1) hipLaunchKernelGGL((sa2_train_kernel<d, c1, c2, 1>), dim3(grid), dim3(256), smem1, st, p);
-    else if (a->stage == 2) hipLaunchKernelGGL((sa2_train_kernel<d, c1, c2, 2>), dim3(grid), dim3(256), smem2, st, p);
-    else {
-      // two waves per SIMD (8-wave workgroups, half a neighbourhood per wave step) unless PFPP_SA_ROWS8=0
-      static const bool rows8 = !(getenv("PFPP_SA_ROWS8") && atoi(getenv("PFPP_SA_ROWS8")) == 0);
-      PFPP_SUPPORTED(!a->sched || rows8, "the padding schedule needs the 8-wave rows kernel (PFPP_SA_ROWS8=0 is set)");
-      const int64_t need8 = (p.G + 7) / 8;
-      if (rows8) hipLaunchKernelGGL((sa_rows8_train_kernel<c2, c3>), dim3((unsigned)(need8 < cap ? need8 : cap)), dim3(512), smem3, st, p);
-      else hipLaunchKernelGGL((sa_rows_train_kernel<c2, c3>), dim3(grid), dim3(256), smem3, st, p);
+    const bool rows3 = !lvl1 && L == 3;          // reads the raw rows stage 2 wrote: only layer 3's operands are needed
+    for (int i = rows3 ? 2 : 0; i < L; ++i) {
+      PFPP_REQUIRE(a->w_hi[i] && a->w_lo[i] && a->bias[i], "weights / bias of a layer this stage computes are missing");
+      PFPP_REQUIRE(pfpp::aligned16(a->w_hi[i]) && pfpp::aligned16(a->w_lo[i]), "planes must be 16-byte aligned");
+    }
+    for (int i = rows3 ? 1 : 0; i + 1 < L; ++i)
+      PFPP_REQUIRE(a->a_mul[i] && a->a_add[i], "finalised BatchNorm affine of an earlier layer is missing");
+    if (lvl1) {
+      PFPP_SUPPORTED(!a->sched, "no padding schedule for the 32-neighbour level");
+      PFPP_SUPPORTED(a->ns == 32 && a->C1 == 64 && a->C2 == 64 && a->C3 == 128, "train-mode chain without features: nsample 32, widths 64/64/128 only");
+      PFPP_REQUIRE(L < 3 || (a->out_max && a->out_min), "stage 3 writes the per-neighbourhood max and min");
+      PFPP_REQUIRE(a->F * a->S < (1ll << 31), "too many neighbourhoods");
+    } else {
+      PFPP_SUPPORTED(a->ns == 64 && a->D == 128 && a->C1 == 128 && a->C2 == 128 && (L < 3 || a->C3 == 256),
+                     "train-mode chain with features: nsample 64, 128 features, widths 128/128/256 only");
+      PFPP_REQUIRE(L < 2 || (a->y_out && pfpp::aligned16(a->y_out)), "stage 2 writes / stage 3 reads the raw layer-2 rows");
+      PFPP_REQUIRE(L < 3 || (a->out_max && a->out_min), "stage 3 writes the per-neighbourhood max and min");
+      PFPP_REQUIRE(pfpp::aligned16(a->feats), "16-byte alignment");
+      PFPP_REQUIRE(a->F * a->S < (1ll << 25), "too many neighbourhoods");
+      PFPP_SUPPORTED(!a->sched || L == 3, "stages 1 and 2 take the padding schedule only in their table-fed form (u_in)");
     }
   }
-  return pfpp::check_launch("pfpp_sa_train_stage");
+  if (a->F == 0) return PFPP_OK;
+
+  const SaTP p = fill_sa(a, table);
+  const int64_t cap = a->max_workgroups > 0 ? a->max_workgroups : 256;       // persistent: one workgroup per CU the stream may use
+  const unsigned per4 = persistent_grid(p.G, 4, cap);                         // 4-wave workgroups, a neighbourhood per wave
+  const float* const no_rows = nullptr;
+  hipStream_t st = pfpp::as_stream(stream);
+  switch (choose_sa_stage((int)a->D, L, table, level)) {
+    case SaKern::Sa1Stage1: return launch_sa<sa1_train_kernel<64, 64, 128, 1>>("sa1_train_kernel<64, 64, 128, 1>", per4, 256, 0, st, p);
+    case SaKern::Sa1Stage2: return launch_sa<sa1_train_kernel<64, 64, 128, 2>>("sa1_train_kernel<64, 64, 128, 2>", per4, 256, 0, st, p);
+    case SaKern::Sa1Stage3: return launch_sa<sa1_train_kernel<64, 64, 128, 3>>("sa1_train_kernel<64, 64, 128, 3>", per4, 256, 0, st, p);
+    case SaKern::Sa2Stage1:
+      return launch_sa<sa2_train_kernel<128, 128, 128, 1>>("sa2_train_kernel<128, 128, 128, 1>", per4, 256, sa_lds(128, gathered(128), 0), st, p);
+    case SaKern::Sa2Stage2:
+      return launch_sa<sa2_train_kernel<128, 128, 128, 2>>("sa2_train_kernel<128, 128, 128, 2>", per4, 256,
+                                                           sa_lds(128, gathered(128), 0) + sa_lds(128, 128, 3), st, p);
+    case SaKern::Rows8:      // two waves per SIMD (8-wave workgroups, half a neighbourhood per wave step)
+      return launch_sa<sa_rows8_train_kernel<128, 256>>("sa_rows8_train_kernel<128, 256>", persistent_grid(p.G, 8, cap), 512, sa_lds(256, 128, 2), st, p);
+    case SaKern::FirstStats128:      // light workgroups: four per CU
+      return launch_sa<sa_first_stats_kernel<128>>("sa_first_stats_kernel<128>", persistent_grid(p.G, 4, 4 * cap), 256, 0, st, p);
+    case SaKern::FirstStats256:
+      return launch_sa<sa_first_stats_kernel<256>>("sa_first_stats_kernel<256>", persistent_grid(p.G, 4, 4 * cap), 256, 0, st, p);
+    case SaKern::Table128:
+      return launch_sa<sa_wide_train_kernel<128, 2, true>>("sa_wide_train_kernel<128, 2, true, false>", rows_grid(cap, 128), 256, sa_lds(128, 128, 9), st, p, no_rows, 128);
+    case SaKern::Table256:
+      return launch_sa<sa_wide_train_kernel<256, 2, true>>("sa_wide_train_kernel<256, 2, true, false>", rows_grid(cap, 256), 256, sa_lds(128, 256, 9), st, p, no_rows, 256);
+    case SaKern::Wide1:
+      return launch_sa<sa_wide_train_kernel<256, 1>>("sa_wide_train_kernel<256, 1, false, false>", rows_grid(cap, 256), 256, sa_lds(128, gathered(256), 0) + 2 * 256 * sizeof(float), st, p, a->y_in, 256);
+    case SaKern::Wide2:
+      return launch_sa<sa_wide_train_kernel<256, 2>>("sa_wide_train_kernel<256, 2, false, false>", rows_grid(cap, 256), 256, sa_lds(128, 256, 2), st, p, a->y_in, 256);
+    case SaKern::Wide3:
+      return launch_sa<sa_wide_train_kernel<256, 3>>("sa_wide_train_kernel<256, 3, false, false>", rows_grid(cap, 512), 256, sa_lds(128, 256, 2), st, p, a->y_in, 512);
+  }
+  return PFPP_EINVAL;      // (not reached: the switch covers the enumeration)
 }
 
 // Eval-mode level with features (sa2), layers 1 and 2 from the per-point table: u [F*N, C1] = [feats | xyz] . W1^T (NO bias: the folded

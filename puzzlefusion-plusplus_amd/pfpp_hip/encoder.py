@@ -7,45 +7,14 @@ ReLU / max-over-nsample epilogue fused in.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+import dataclasses
+import enum
+from typing import Callable, Dict, Optional
 
 import torch
 
 from . import ops
 from .packing import PW, fold_conv_bn, pack_sa_first
-
-import os as _os
-
-BN_FUSED = _os.environ.get("PFPP_BN_FUSED", "1") == "1"
-# the grouped neighbourhoods [F*S*ns, D+4] are never written out: the first convolution's GEMM gathers its A rows from
-# the level's feature table (pfpp_gemm_args.gather_*); 0 = materialise them with pfpp_group_gather as before
-GATHER_FUSED = _os.environ.get("PFPP_GATHER_FUSED", "1") == "1"
-# eval mode, first level (no input features): grouping + the three folded conv/BN/ReLU + the max in one kernel
-SA_FUSED = _os.environ.get("PFPP_SA_FUSED", "1") == "1"
-
-# train mode: levels 1 and 2 as recomputing chain launches (csrc/sa_train.hip) instead of layer-wise GEMMs over [rows, C] activations
-SA_TRAIN_CHAIN = _os.environ.get("PFPP_SA_TRAIN_CHAIN", "1") == "1"
-
-# first layer of the levels with features by linearity: conv1 per POINT once (ops.sa_first_table), its value on a grouped row is
-# U[point] - W_xyz . centroid — the grouped first convolution (42 / 33 GFLOP at levels 2 / 3) is never computed in train mode
-SA_TRAIN_UTAB = _os.environ.get("PFPP_SA_TRAIN_UTAB", "1") == "1"
-# the same in eval mode: 0 off, 1 level 2 (ops.sa_mlp2_table), 2 levels 2 and 3 (ops.sa_table_planes feeds level 3's plane GEMMs)
-SA_EVAL_UTAB = int(_os.environ.get("PFPP_SA_EVAL_UTAB", "2"))
-SA_TRAIN_WIDE = _os.environ.get("PFPP_SA_TRAIN_WIDE", "1") == "1"     # level 3 in train mode as rows launches (sa_wide_train_kernel)
-
-# eval-mode level 3 on the rows kernels of the train-mode chain (0 = elementwise pass + two tiled plane GEMMs: the cross-check), from
-# this many grouped rows up (a handful of fragments stays on the tiled path: a persistent rows workgroup loads a 140 KB weight slice first)
-SA_EVAL_ROWS = _os.environ.get("PFPP_SA_EVAL_ROWS", "1") == "1"
-SA_EVAL_ROWS_MIN = int(_os.environ.get("PFPP_SA_EVAL_ROWS_MIN", "0"))
-# the same for level 2 (128 + 3 -> 128 -> 128 -> 256: stage 2 writes the raw second-layer rows, stage 3 keeps the third layer's weights in LDS)
-SA_EVAL_ROWS2 = _os.environ.get("PFPP_SA_EVAL_ROWS2", "1") == "1"
-SA_EVAL_ROWS2_MIN = int(_os.environ.get("PFPP_SA_EVAL_ROWS2_MIN", "200000"))      # one puzzle in flight (65 K rows): neutral, stays tiled
-SAMPLE_FUSED = _os.environ.get("PFPP_SAMPLE_FUSED", "1") != "0"     # FPS + ball query of the three levels in one kernel
-SAMPLE_FUSED_MIN = int(_os.environ.get("PFPP_SAMPLE_FUSED_MIN", "32"))    # ... from this many fragments up
-
-# 64-neighbour levels: neighbourhoods the ball query padded beyond their first 32 slots are taken as one half (ops.sa_pad_schedule)
-SA_PAD_SKIP = _os.environ.get("PFPP_SA_PAD_SKIP", "1") != "0"
-SA_PAD_SKIP_MIN = int(_os.environ.get("PFPP_SA_PAD_SKIP_MIN", "2048"))     # ... from this many neighbourhoods up (one puzzle in flight: the schedule's two launches cost more than they save)
 
 # (name, npoint, radius, nsample) — vqvae/model/modules/pn2.py:16-18
 SA_LEVELS = (("sa1", 256, 0.2, 32), ("sa2", 128, 0.4, 64), ("sa3", None, 0.8, 64))
@@ -100,11 +69,94 @@ def pack_encoder_train(sd: Dict[str, torch.Tensor], prefix: str = "") -> Dict[st
     return out
 
 
-def _sa_chain_train(pk, name: str, grp, nsample: int) -> torch.Tensor:
+# ----------------------------------------------------------------------------- which path a level takes
+# level-2 eval on the rows kernels from this many grouped rows up: one puzzle in flight (65 K rows) is neutral and stays on
+# sa_mlp2_table + GEMM (a persistent rows workgroup loads a 140 KB weight slice first)
+EVAL_ROWS_MIN_ROWS_128 = 200_000
+# padding schedule of the 64-neighbour levels from this many neighbourhoods up (one puzzle in flight: its two launches cost more than they save)
+PAD_SCHEDULE_MIN_NEIGHBOURHOODS = 2048
+# FPS + ball query of the three levels in one kernel from this many fragments up (a handful of fragments — one puzzle in flight — is
+# latency-bound either way; there the per-level kernels' wider ball-query grids win: 171 vs 189 us at F = 8)
+SAMPLE_FUSED_MIN_FRAGMENTS = 32
+
+
+class SaPath(enum.Enum):
+    TRAIN_CHAIN = "recomputing chain launches (csrc/sa_train.hip): the [rows, C] activations of the layer-wise form are not written"
+    TRAIN_LAYERWISE = "layer-wise GEMMs with the batch statistics in their epilogues and normalise + ReLU in the consumer's A loader"
+    TRAIN_UNFUSED = "GEMM, bn_stats, bn_apply per layer"
+    EVAL_MLP3 = "grouping + the three folded conv/BN/ReLU + the max in one kernel (ops.sa_mlp3_fused)"
+    EVAL_ROWS = "the rows kernels of the train-mode chain with the folded BatchNorm as the layers' affines (_sa_rows_eval)"
+    EVAL_MLP2 = "grouping + layers 1 and 2 in one kernel, layer 3 (+ max over nsample) as a GEMM"
+    EVAL_TILED = "one GEMM per layer"
+
+
+@dataclasses.dataclass(frozen=True)
+class SaPlan:
+    path: SaPath
+    # the grouped neighbourhoods [F*S*ns, D+4] are never written out: the first convolution's GEMM gathers its A rows from the level's
+    # feature table (pfpp_gemm_args.gather_*); False = materialise them with pfpp_group_gather
+    gather_in_gemm: bool
+    # first layer of a level with features by linearity: conv1 per POINT once (ops.sa_first_table), its value on a grouped row is
+    # U[point] - W_xyz . centroid — the grouped first convolution (42 / 33 GFLOP at levels 2 / 3) is never computed
+    table_first: bool
+    # 64-neighbour levels: neighbourhoods the ball query padded beyond their first 32 slots are taken as one half (ops.sa_pad_schedule)
+    pad_schedule: bool
+
+
+def choose_sa(*, train: bool, gemm_mode: str, split_act: bool, single_pass: bool, D: int, nsample: int, widths, neighbourhoods: int,
+              grouped: bool = True) -> SaPlan:
+    """The path of one set-abstraction level, from the facts of the call alone: D input features (0 = none), widths = the three layer
+    widths, neighbourhoods = F * npoint, grouped = the caller holds the grouping tuple (False: materialised rows only,
+    utils/pn2_utils.py).  tests/test_sa_choice_host.py pins the table."""
+    widths = tuple(widths)
+    f16x3 = gemm_mode == "f16x3"
+    gather = f16x3 and D % 32 == 0
+    level = {(0, 32, (64, 64, 128)): 1, (128, 64, (128, 128, 256)): 2, (256, 64, (256, 256, 512)): 3}.get((D, nsample, widths))
+    pad = nsample == 64 and neighbourhoods >= PAD_SCHEDULE_MIN_NEIGHBOURHOODS
+    if train:
+        if f16x3 and grouped and level is not None:
+            return SaPlan(SaPath.TRAIN_CHAIN, True, D > 0, D > 0 and pad)
+        return SaPlan(SaPath.TRAIN_LAYERWISE if f16x3 else SaPath.TRAIN_UNFUSED, gather and grouped, False, False)
+    planes = split_act and f16x3           # activations between the layers as split-f16 planes
+    if gather and level == 1:
+        return SaPlan(SaPath.EVAL_MLP3, True, False, False)
+    if gather and planes and not single_pass and (level == 3 or (level == 2 and neighbourhoods * nsample >= EVAL_ROWS_MIN_ROWS_128)):
+        return SaPlan(SaPath.EVAL_ROWS, True, True, pad)
+    if gather and D == 128 and nsample == 64 and widths[:2] == (128, 128):
+        return SaPlan(SaPath.EVAL_MLP2, True, planes, False)
+    return SaPlan(SaPath.EVAL_TILED, gather, gather and planes and nsample == 64 and (D, widths[0]) in ((256, 256), (128, 128)), False)
+
+
+def fused_sampling(fragments: int, supported: bool) -> bool:
+    """ops.sample_levels (the sampling chain of all three levels in one launch) or the per-level kernels"""
+    return supported and fragments >= SAMPLE_FUSED_MIN_FRAGMENTS
+
+
+def sa_plan(pk, name: str, nsample: int, neighbourhoods: int, feats: Optional[torch.Tensor], choose: Callable[..., SaPlan] = choose_sa) -> SaPlan:
+    """`choose` on the facts of this call: the numeric mode of ops and the level's shape"""
+    return choose(train=bool(pk.get("train", False)), gemm_mode=ops.GEMM_MODE, split_act=ops.split_mode(), single_pass=ops.SINGLE_PASS,
+                  D=0 if feats is None else feats.shape[2], nsample=nsample, widths=tuple(pk[f"{name}.w{i}"].N for i in range(3)),
+                  neighbourhoods=neighbourhoods)
+
+
+# Stages of the recomputing chain per level kind (D, table_first): (u_in, y_out, y_in) of stages 1-3, where y_out / y_in name the buffer
+# of raw rows ("y1", "y2": that layer's pre-activations [rows, C]) handed over under that argument.  Stage 3 also gets out_max / out_min.
+_CHAIN_STAGES = {
+    # no features: every stage recomputes from the points, nothing but the sums (and the pooled max / min) is written
+    (0, False): ((False, None, None), (False, None, None), (False, None, None)),
+    # 128 features: stage 2 writes the raw second-layer rows, stage 3 (its weights resident in LDS) reads them through the same argument
+    (128, True): ((True, None, None), (True, "y2", None), (False, "y2", None)),
+    (128, False): ((False, None, None), (False, "y2", None), (False, "y2", None)),
+    # 256 features: one rows launch per layer (no two weight matrices fit in LDS), the previous layer's raw rows come in as y_in
+    (256, True): ((True, None, None), (True, "y2", None), (False, None, "y2")),
+    (256, False): ((False, "y1", None), (False, "y2", "y1"), (False, None, "y2")),
+}
+
+
+def _sa_chain_train(pk, name: str, grp, nsample: int, plan: SaPlan) -> torch.Tensor:
     """train-mode level by recomputation (csrc/sa_train.hip): one persistent chain launch per layer; stage k recomputes layers
     1..k-1 in registers and produces layer k's batch statistics — the [rows, C] activations of the layer-wise form are never
-    written (level 1) / only the raw second-layer rows are (level 2: its third convolution's weights do not fit in LDS next to the
-    others, so stage 3 reads those rows back with that layer's weights resident)"""
+    written (level 1) / only the raw second-layer rows are (levels 2 and 3 with the per-point first layer)"""
     from . import train_ops as T
 
     xyz, new_xyz, feats, ball = grp
@@ -113,15 +165,12 @@ def _sa_chain_train(pk, name: str, grp, nsample: int) -> torch.Tensor:
     rows = F * S * nsample
     ws = [pk[f"{name}.w{i}"] for i in range(3)]
     bs = [pk[f"{name}.b{i}"] for i in range(3)]
-    n_chain = 3
     affs = []
-    y2 = mx = mn = None
-    wide = feats is not None and feats.shape[2] == 256       # level 3: one rows launch per layer (no two weight matrices fit in LDS)
-    y_prev = None
-    utab = ops.sa_first_table(xyz, feats, ws[0], bs[0]) if (SA_TRAIN_UTAB and feats is not None) else None
-    # the padding schedule goes to all stages of the level or to none: with the per-point table every stage takes it
-    sched = ops.sa_pad_schedule(ball) if (SA_PAD_SKIP and utab is not None and nsample == 64 and F * S >= SA_PAD_SKIP_MIN) else None
-    for i in range(n_chain):
+    utab = ops.sa_first_table(xyz, feats, ws[0], bs[0]) if plan.table_first else None
+    # the padding schedule goes to all stages of the level or to none (the raw rows of a skipped half are neither written nor read)
+    sched = ops.sa_pad_schedule(ball) if plan.pad_schedule else None
+    mx, mn, y = None, None, {}
+    for i, (table, y_out, y_in) in enumerate(_CHAIN_STAGES[0 if feats is None else feats.shape[2], plan.table_first]):
         Cout = ws[i].N
         st = pk.get(f"{name}.stats{i}")
         if st is None:
@@ -129,41 +178,29 @@ def _sa_chain_train(pk, name: str, grp, nsample: int) -> torch.Tensor:
         if i == 2:
             mx = torch.empty((F * S, Cout), dtype=torch.float32, device=dev)
             mn = torch.empty((F * S, Cout), dtype=torch.float32, device=dev)
-        if utab is not None and i < 2:
-            # first layer by linearity: statistics of U[idx] - W_xyz . centroid (no matrix work), then the second layer from gathered rows
-            y_cur = torch.empty((rows, Cout), dtype=torch.float32, device=dev) if i == 1 else None
-            ops.sa_train_stage(i + 1, xyz, new_xyz, feats, ball, ws, bs, affs, st, y_out=y_cur, u_in=utab, sched=sched)
-            y_prev = y2 = y_cur
-        elif wide:
-            y_cur = torch.empty((rows, Cout), dtype=torch.float32, device=dev) if i < 2 else None
-            ops.sa_train_stage(i + 1, xyz, new_xyz, feats, ball, ws, bs, affs, st, y_out=y_cur, y_in=y_prev,
-                               out_max=mx if i == 2 else None, out_min=mn if i == 2 else None, sched=sched)
-            y_prev = y_cur
-        else:
-            if feats is not None and i == 1:
-                y2 = torch.empty((rows, Cout), dtype=torch.float32, device=dev)
-            # level 2: stage 2 writes the raw second-layer rows, stage 3 (weights of the third convolution resident in LDS) reads them
-            ops.sa_train_stage(i + 1, xyz, new_xyz, feats, ball, ws, bs, affs, st, y_out=y2 if i >= 1 else None,
-                               out_max=mx if i == 2 else None, out_min=mn if i == 2 else None, sched=sched if i == 2 else None)
+        if y_out is not None and y_out not in y:
+            y[y_out] = torch.empty((rows, Cout), dtype=torch.float32, device=dev)
+        ops.sa_train_stage(i + 1, xyz, new_xyz, feats, ball, ws, bs, affs, st, y_out=y.get(y_out), y_in=y.get(y_in), out_max=mx, out_min=mn,
+                           u_in=utab if table else None, sched=sched)
         affs.append(T.bn_finalize(st, rows, pk[f"{name}.g{i}"], pk[f"{name}.be{i}"], pk[f"{name}.rm{i}"], pk[f"{name}.rv{i}"],
                                   momentum=0.1, eps=1e-5))
     torch._foreach_add_([pk[f"{name}.nbt{i}"] for i in range(3)], 1)
     return T.bn_minmax_apply(mx, mn, affs[2][0], affs[2][1])
 
 
-def _sa_mlp_train(pk, name: str, A: Optional[torch.Tensor], nsample: int, grp=None) -> torch.Tensor:
+def _sa_mlp_train(pk, name: str, A: Optional[torch.Tensor], nsample: int, grp=None, plan: Optional[SaPlan] = None) -> torch.Tensor:
     """3 x [1x1 conv -> BatchNorm (batch statistics, running buffers updated) -> ReLU], max over nsample
-    (utils/pn2_utils.py:210-216 with the module in .train())"""
+    (utils/pn2_utils.py:210-216 with the module in .train()).  A = the materialised grouped rows [F*S*ns, D+4], or None with the grouping
+    tuple in grp; without a plan (utils/pn2_utils.py: materialised rows only) the mode of ops decides alone"""
     from . import train_ops as T
 
-    if ops.GEMM_MODE == "f16x3" and BN_FUSED and SA_TRAIN_CHAIN and grp is not None:
-        widths = tuple(pk[f"{name}.w{i}"].N for i in range(3))
-        feats = grp[2]
-        if (feats is None and nsample == 32 and widths == (64, 64, 128)) or \
-           (feats is not None and nsample == 64 and feats.shape[2] == 128 and widths == (128, 128, 256)) or \
-           (SA_TRAIN_WIDE and feats is not None and nsample == 64 and feats.shape[2] == 256 and widths == (256, 256, 512)):
-            return _sa_chain_train(pk, name, grp, nsample)
-    if ops.GEMM_MODE == "f16x3" and BN_FUSED:
+    if plan is None:
+        plan = choose_sa(train=True, gemm_mode=ops.GEMM_MODE, split_act=ops.split_mode(), single_pass=ops.SINGLE_PASS, D=A.shape[1] - 4,
+                         nsample=nsample, widths=tuple(pk[f"{name}.w{i}"].N for i in range(3)), neighbourhoods=A.shape[0] // nsample,
+                         grouped=False)
+    if plan.path is SaPath.TRAIN_CHAIN:
+        return _sa_chain_train(pk, name, grp, nsample, plan)
+    if plan.path is SaPath.TRAIN_LAYERWISE:
         # fused form: batch statistics come out of the producing GEMM's epilogue, normalise+ReLU is applied by the
         # consuming GEMM while it stages its A tiles, and the last layer emits per-group max AND min instead of
         # its [rows, C] activation (max_p relu(a*y_p + b) = relu(a*(a >= 0 ? max_p y_p : min_p y_p) + b))
@@ -196,7 +233,7 @@ def _sa_mlp_train(pk, name: str, A: Optional[torch.Tensor], nsample: int, grp=No
     return h
 
 
-def _sa_rows_eval(pk, name: str, grp, nsample: int) -> torch.Tensor:
+def _sa_rows_eval(pk, name: str, grp, nsample: int, plan: SaPlan) -> torch.Tensor:
     """eval-mode level with input features (sa3: 256 + 3 -> 256 -> 256 -> 512; sa2: 128 + 3 -> 128 -> 128 -> 256; 64 neighbours) on the ROWS kernels of the train-mode chain
     (csrc/sa_train.hip sa_wide_train_kernel<256, 2, UG> / <256, 3>: a workgroup keeps a 128-column slice of the layer's weight planes in
     LDS for its lifetime, a wave streams 32 rows at a time) instead of an elementwise pass + two tiled plane GEMMs with their
@@ -220,21 +257,20 @@ def _sa_rows_eval(pk, name: str, grp, nsample: int) -> torch.Tensor:
     zb, st = sc
     u = ops.sa_first_table(xyz, feats, ws[0], None)
     y2 = torch.empty((rows, ws[1].N), dtype=torch.float32, device=dev)
-    sched = ops.sa_pad_schedule(ball) if (SA_PAD_SKIP and F * S >= SA_PAD_SKIP_MIN) else None      # padded second halves add nothing to a max / min
+    sched = ops.sa_pad_schedule(ball) if plan.pad_schedule else None      # padded second halves add nothing to a max / min
     ops.sa_train_stage(2, xyz, new_xyz, feats, ball, ws, zb, aff[:1], st[1], y_out=y2, u_in=u, sched=sched)
     mx = torch.empty((F * S, ws[2].N), dtype=torch.float32, device=dev)
     mn = torch.empty((F * S, ws[2].N), dtype=torch.float32, device=dev)
-    if feats.shape[2] == 256:      # level 3: one rows launch per layer, the previous layer's raw rows come in as y_in
-        ops.sa_train_stage(3, xyz, new_xyz, feats, ball, ws, zb, aff[:2], st[2], y_in=y2, out_max=mx, out_min=mn, sched=sched)
-    else:                          # level 2: stage 3 reads the raw rows stage 2 wrote, its 256 x 128 weight planes resident in LDS
-        ops.sa_train_stage(3, xyz, new_xyz, feats, ball, ws, zb, aff[:2], st[2], y_out=y2, out_max=mx, out_min=mn, sched=sched)
+    # stage 3 as in _CHAIN_STAGES: 256 features read the previous layer's raw rows as y_in, 128 features through y_out
+    y3 = dict(y_in=y2) if feats.shape[2] == 256 else dict(y_out=y2)
+    ops.sa_train_stage(3, xyz, new_xyz, feats, ball, ws, zb, aff[:2], st[2], out_max=mx, out_min=mn, sched=sched, **y3)
     return T.bn_minmax_apply(mx, mn, aff[2][0], aff[2][1])
 
 
 def set_abstraction(pk, name: str, npoint: int, radius: float, nsample: int, xyz: torch.Tensor,
-                    feats: Optional[torch.Tensor], capture: Optional[dict] = None, sampled=None):
+                    feats: Optional[torch.Tensor], capture: Optional[dict] = None, sampled=None, plan: Optional[SaPlan] = None):
     """xyz [F,N,3], feats [F,N,D] or None -> new_xyz [F,S,3], new_feats [F,S,C3].  sampled = (fps_idx, new_xyz, ball_idx) when the
-    sampling of all levels was done up front (ops.sample_levels)"""
+    sampling of all levels was done up front (ops.sample_levels); plan = the path to take (default: choose_sa on this call)"""
     F = xyz.shape[0]
     if sampled is not None:
         fps_idx, new_xyz, ball = sampled
@@ -242,90 +278,53 @@ def set_abstraction(pk, name: str, npoint: int, radius: float, nsample: int, xyz
         ops.check_fps_ratio(npoint, xyz.shape[1])
         fps_idx, new_xyz = ops.fps(xyz, npoint)
         ball = ops.ball_query(xyz, new_xyz, radius, nsample)
-    fused = GATHER_FUSED and ops.GEMM_MODE == "f16x3" and (feats is None or feats.shape[2] % 32 == 0)
-    A = None if fused else ops.group_gather(xyz, new_xyz, feats, ball)
+    if plan is None:
+        plan = sa_plan(pk, name, nsample, F * npoint, feats)
+    A = None if plan.gather_in_gemm else ops.group_gather(xyz, new_xyz, feats, ball)
     grp = (xyz, new_xyz, None if feats is None else feats.contiguous(), ball)
-    if pk.get("train", False):
-        if fused and not BN_FUSED:
-            A = ops.group_gather(xyz, new_xyz, feats, ball)
-        h = _sa_mlp_train(pk, name, A, nsample, grp)
-        del A
-    elif (SA_FUSED and fused and feats is None and nsample == 32
-          and (pk[f"{name}.w0"].N, pk[f"{name}.w1"].N, pk[f"{name}.w2"].N) == (64, 64, 128)):
-        h = ops.sa_mlp3_fused(xyz, new_xyz, ball, pk[f"{name}.w0"], pk[f"{name}.w1"], pk[f"{name}.w2"], pk[f"{name}.s0"], pk[f"{name}.t0"],
-                              pk[f"{name}.s1"], pk[f"{name}.t1"], pk[f"{name}.s2"], pk[f"{name}.t2"])
-        new_feats = h.view(F, npoint, -1)
-        if capture is not None:
-            capture[f"{name}.fps_idx"] = fps_idx
-            capture[f"{name}.ball_idx"] = ball
-            capture[f"{name}.new_xyz"] = new_xyz
-            capture[f"{name}.new_points"] = new_feats
-        return new_xyz, new_feats
-    elif (SA_EVAL_ROWS and fused and ops.split_mode() and ops.GEMM_MODE == "f16x3" and not ops.SINGLE_PASS and feats is not None and nsample == 64
-          and feats.shape[2] == 256 and (pk[f"{name}.w0"].N, pk[f"{name}.w1"].N, pk[f"{name}.w2"].N) == (256, 256, 512)
-          and F * npoint * nsample >= SA_EVAL_ROWS_MIN):
-        h = _sa_rows_eval(pk, name, grp, nsample)
-    elif (SA_EVAL_ROWS2 and fused and ops.split_mode() and ops.GEMM_MODE == "f16x3" and not ops.SINGLE_PASS and feats is not None and nsample == 64
-          and feats.shape[2] == 128 and (pk[f"{name}.w0"].N, pk[f"{name}.w1"].N, pk[f"{name}.w2"].N) == (128, 128, 256)
-          and F * npoint * nsample >= SA_EVAL_ROWS2_MIN):
-        h = _sa_rows_eval(pk, name, grp, nsample)
-    elif (SA_FUSED and fused and feats is not None and nsample == 64 and feats.shape[2] == 128
-          and (pk[f"{name}.w0"].N, pk[f"{name}.w1"].N) == (128, 128)):
-        # level 2: grouping + layers 1 and 2 in one kernel, layer 3 (+ max over nsample) as a GEMM
-        # the activation goes to layer 3 as split-f16 planes (same bytes as fp32): layer 3 is then the LDS-DMA plane GEMM with no
-        # conversion work in its loop
-        if SA_EVAL_UTAB and ops.split_mode() and ops.GEMM_MODE == "f16x3":
-            # first layer per point (linear): the grouped first convolution is not computed (ops.sa_mlp2_table)
-            h = ops.sa_mlp2_table(xyz, new_xyz, grp[2], ball, pk[f"{name}.w0"], pk[f"{name}.w1"], pk[f"{name}.s0"], pk[f"{name}.t0"],
-                                  pk[f"{name}.s1"], pk[f"{name}.t1"])
-        else:
-            h = ops.sa_mlp2_fused(xyz, new_xyz, grp[2], ball, pk[f"{name}.w0"], pk[f"{name}.w1"], pk[f"{name}.s0"], pk[f"{name}.t0"],
-                                  pk[f"{name}.s1"], pk[f"{name}.t1"], as_planes=ops.split_mode())
-        h = ops.linear(h, pk[f"{name}.w2"], scale=pk[f"{name}.s2"], shift=pk[f"{name}.t2"], act="relu", pool=nsample)
-        new_feats = h.view(F, npoint, -1)
-        if capture is not None:
-            capture[f"{name}.fps_idx"] = fps_idx
-            capture[f"{name}.ball_idx"] = ball
-            capture[f"{name}.new_xyz"] = new_xyz
-            capture[f"{name}.new_points"] = new_feats
-        return new_xyz, new_feats
+    w, s, t = ([pk.get(f"{name}.{k}{i}") for i in range(3)] for k in "wst")
+    if plan.path in (SaPath.TRAIN_CHAIN, SaPath.TRAIN_LAYERWISE, SaPath.TRAIN_UNFUSED):
+        h = _sa_mlp_train(pk, name, A, nsample, grp, plan)
+    elif plan.path is SaPath.EVAL_MLP3:
+        h = ops.sa_mlp3_fused(xyz, new_xyz, ball, w[0], w[1], w[2], s[0], t[0], s[1], t[1], s[2], t[2])
+    elif plan.path is SaPath.EVAL_ROWS:
+        h = _sa_rows_eval(pk, name, grp, nsample, plan)
+    elif plan.path is SaPath.EVAL_MLP2:
+        # first layer per point (ops.sa_mlp2_table: the grouped first convolution is not computed): the activation then goes to layer 3
+        # as split-f16 planes (same bytes as fp32), the LDS-DMA plane GEMM with no conversion work in its loop
+        mlp2 = ops.sa_mlp2_table if plan.table_first else ops.sa_mlp2_fused
+        h = mlp2(xyz, new_xyz, grp[2], ball, w[0], w[1], s[0], t[0], s[1], t[1])
+        h = ops.linear(h, w[2], scale=s[2], shift=t[2], act="relu", pool=nsample)
     else:
-        rows = F * npoint * nsample
-        sp = ops.split_mode() and ops.GEMM_MODE == "f16x3"      # activations between the layers as split-f16 planes
-        if (fused and sp and SA_EVAL_UTAB >= 2 and feats is not None and nsample == 64
-                and (feats.shape[2], pk[f"{name}.w0"].N) in ((256, 256), (128, 128))):
+        # activations between the layers as split-f16 planes
+        planes = (lambda i: ops.SplitAct.empty(F * npoint * nsample, w[i].N, xyz.device)) if ops.split_mode() else (lambda i: None)
+        if plan.table_first:
             # first layer per point (linear), then an elementwise pass over the grouped rows (ops.sa_table_planes)
-            h = ops.sa_table_planes(grp[0], grp[1], grp[2], grp[3], pk[f"{name}.w0"], pk[f"{name}.s0"], pk[f"{name}.t0"])
-        elif fused:
-            h = ops.grouped_linear(*grp, pk[f"{name}.w0"], scale=pk[f"{name}.s0"], shift=pk[f"{name}.t0"], act="relu",
-                                   out=ops.SplitAct.empty(rows, pk[f"{name}.w0"].N, xyz.device) if sp else None)
+            h = ops.sa_table_planes(*grp, w[0], s[0], t[0])
+        elif A is None:
+            h = ops.grouped_linear(*grp, w[0], scale=s[0], shift=t[0], act="relu", out=planes(0))
         else:
-            h = ops.linear(A, pk[f"{name}.w0"], scale=pk[f"{name}.s0"], shift=pk[f"{name}.t0"], act="relu",
-                           out=ops.SplitAct.empty(rows, pk[f"{name}.w0"].N, xyz.device) if sp else None)
+            h = ops.linear(A, w[0], scale=s[0], shift=t[0], act="relu", out=planes(0))
         del A
-        h = ops.linear(h, pk[f"{name}.w1"], scale=pk[f"{name}.s1"], shift=pk[f"{name}.t1"], act="relu",
-                       out=ops.SplitAct.empty(rows, pk[f"{name}.w1"].N, xyz.device) if sp else None)
-        h = ops.linear(h, pk[f"{name}.w2"], scale=pk[f"{name}.s2"], shift=pk[f"{name}.t2"], act="relu", pool=nsample)
+        h = ops.linear(h, w[1], scale=s[1], shift=t[1], act="relu", out=planes(1))
+        h = ops.linear(h, w[2], scale=s[2], shift=t[2], act="relu", pool=nsample)
     new_feats = h.view(F, npoint, -1)
     if capture is not None:
-        capture[f"{name}.fps_idx"] = fps_idx
-        capture[f"{name}.ball_idx"] = ball
-        capture[f"{name}.new_xyz"] = new_xyz
-        capture[f"{name}.new_points"] = new_feats
+        capture.update({f"{name}.fps_idx": fps_idx, f"{name}.ball_idx": ball, f"{name}.new_xyz": new_xyz, f"{name}.new_points": new_feats})
     return new_xyz, new_feats
 
 
-def pn2_encode(pk, pts: torch.Tensor, num_point: int = 25, capture: Optional[dict] = None):
-    """pts [F,N,3] (already rotated) -> z_e [F,L,64], xyz [F,L,3]   (pn2.py:57-68)"""
+def pn2_encode(pk, pts: torch.Tensor, num_point: int = 25, capture: Optional[dict] = None, choose: Callable[..., SaPlan] = choose_sa):
+    """pts [F,N,3] (already rotated) -> z_e [F,L,64], xyz [F,L,3]   (pn2.py:57-68).  choose: choose_sa or a function of the same
+    signature (the tests' cross-check paths)"""
     xyz, feats = pts, None
     # the sampling chain of all three levels depends on coordinates only: one launch (FPS x 3 + ball query x 3 per fragment)
     lv = tuple((npoint or num_point, radius, nsample) for _, npoint, radius, nsample in SA_LEVELS)
-    # (a handful of fragments — one puzzle in flight — is latency-bound either way; there the per-level kernels' wider ball-query grids
-    # win: 171 vs 189 us at F = 8)
-    sampled = (ops.sample_levels(pts, lv) if (SAMPLE_FUSED and pts.shape[0] >= SAMPLE_FUSED_MIN and ops.sample_levels_supported(pts.shape[1], lv))
-               else (None,) * 3)
+    sampled = ops.sample_levels(pts, lv) if fused_sampling(pts.shape[0], ops.sample_levels_supported(pts.shape[1], lv)) else (None,) * 3
     for (name, npoint, radius, nsample), smp in zip(SA_LEVELS, sampled):
-        xyz, feats = set_abstraction(pk, name, npoint or num_point, radius, nsample, xyz, feats, capture, sampled=smp)
+        npoint = npoint or num_point
+        plan = sa_plan(pk, name, nsample, xyz.shape[0] * npoint, feats, choose)
+        xyz, feats = set_abstraction(pk, name, npoint, radius, nsample, xyz, feats, capture, sampled=smp, plan=plan)
     F, L, C3 = feats.shape
     z_e = ops.linear(feats.view(F * L, C3), pk["conv6.w"], pk["conv6.b"]).view(F, L, -1)
     return z_e, xyz

@@ -29,13 +29,13 @@ import torch
 from . import _lib, ops
 from . import train_ops as T
 from ._lib import check
+from .encoder import SA_LEVELS
 from .ops import _chk, _ptr, _stream
 from .packing import PW, pack_sa_first, round_up
 from .train import DenoiserTrainEngine, FlatParams, TrainContext, _f32c, _pw_view
 
 _f32 = torch.float32
 MAX_FRAGMENTS = 2048          # batch statistics need all fragments of a step in one pass (as the train-mode encode)
-SA_LEVELS = (("sa1", 256, 0.2, 32), ("sa2", 128, 0.4, 64), ("sa3", None, 0.8, 64))      # pn2.py:16-18
 
 
 # ------------------------------------------------------------------------------------------------ tensor-level wrappers

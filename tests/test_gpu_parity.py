@@ -1891,11 +1891,14 @@ def test_sa_table_planes_equals_grouped_first_layer(dev, F, N, S, D):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("F,N,S,D", [(3, 128, 25, 256), (40, 128, 25, 256), (3, 256, 128, 128), (12, 256, 128, 128)])
-def test_sa_rows_eval_rows_equals_the_tiled_level(dev, F, N, S, D, monkeypatch):
+def test_sa_rows_eval_rows_equals_the_tiled_level(dev, F, N, S, D):
     """eval-mode level 3 (256 + 3 -> 256 -> 256 -> 512, 64 neighbours, folded BatchNorm, max over the neighbourhood) on the rows kernels
     of the train-mode chain (encoder._sa_rows_eval: pfpp_sa_train_stage with the folded scale / shift as affines, max / min trick) against
     the elementwise pass + two tiled plane GEMMs it replaces and a float64 restatement of pn2_utils.py:203-216 in .eval(); negative
-    scales included (the max / min selection)"""
+    scales included (the max / min selection).  Both paths by explicit plan: these sizes are below the row counts from which the
+    product takes the rows kernels (level 2) and builds the padding schedule"""
+    import dataclasses
+
     from pfpp_hip import encoder, ops
     from pfpp_hip.packing import PW, pack_sa_first
 
@@ -1911,7 +1914,6 @@ def test_sa_rows_eval_rows_equals_the_tiled_level(dev, F, N, S, D, monkeypatch):
     live = torch.randint(1, 33, (F, S), generator=g)
     live = torch.where(torch.rand(F, S, generator=g) < 0.4, live, torch.randint(33, 65, (F, S), generator=g))
     idx = torch.where(torch.arange(ns).view(1, 1, ns) < live.unsqueeze(-1), idx, idx[:, :, :1])
-    monkeypatch.setattr(encoder, "SA_PAD_SKIP_MIN", 0)
     widths = (D, D, 2 * D)
     w_ref = [torch.randn(D, D + 3, generator=g) * 0.06, torch.randn(D, D, generator=g) * 0.06, torch.randn(2 * D, D, generator=g) * 0.06]
     sc = [torch.rand(c, generator=g) + 0.5 for c in widths]
@@ -1923,12 +1925,13 @@ def test_sa_rows_eval_rows_equals_the_tiled_level(dev, F, N, S, D, monkeypatch):
         pk[f"{lvl}.w{i}"] = PW(d(pack_sa_first(w_ref[0], D) if i == 0 else w_ref[i]).contiguous(), prescale=False)
         pk[f"{lvl}.s{i}"], pk[f"{lvl}.t{i}"] = d(sc[i]), d(sh[i])
     outs = []
-    for rows_path in (False, True):
-        monkeypatch.setattr(encoder, "SA_EVAL_ROWS", rows_path)
-        monkeypatch.setattr(encoder, "SA_EVAL_ROWS2", rows_path)
-        monkeypatch.setattr(encoder, "SA_EVAL_ROWS2_MIN", 0)
-        monkeypatch.setattr(encoder, "SA_EVAL_ROWS_MIN", 0)
-        _, h = encoder.set_abstraction(pk, lvl, S, radius, ns, d(xyz), d(feats), sampled=(None, d(new_xyz), d(idx)))
+    base = encoder.sa_plan(pk, lvl, ns, F * S, feats)
+    assert base.gather_in_gemm and base.table_first
+    rows_plan = dataclasses.replace(base, path=encoder.SaPath.EVAL_ROWS, pad_schedule=True)
+    # what the level took before the rows kernels: level 3 the table-fed elementwise pass + two GEMMs, level 2 sa_mlp2_table + one GEMM
+    tiled_plan = dataclasses.replace(base, path=encoder.SaPath.EVAL_TILED if D == 256 else encoder.SaPath.EVAL_MLP2, pad_schedule=False)
+    for plan in (tiled_plan, rows_plan):
+        _, h = encoder.set_abstraction(pk, lvl, S, radius, ns, d(xyz), d(feats), sampled=(None, d(new_xyz), d(idx)), plan=plan)
         outs.append(h.clone())
     tiled, rows = outs
     assert f"{lvl}._rows_eval" in pk and rows.shape == tiled.shape == (F, S, 2 * D)
@@ -1942,9 +1945,7 @@ def test_sa_rows_eval_rows_equals_the_tiled_level(dev, F, N, S, D, monkeypatch):
     tol = 2e-5 * y.abs().max().item()
     assert (rows.double().cpu() - y).abs().max().item() < tol
     assert (rows - tiled).abs().max().item() < tol
-    monkeypatch.setattr(encoder, "SA_EVAL_ROWS", True)
-    monkeypatch.setattr(encoder, "SA_EVAL_ROWS2", True)
-    _, again = encoder.set_abstraction(pk, lvl, S, radius, ns, d(xyz), d(feats), sampled=(None, d(new_xyz), d(idx)))
+    _, again = encoder.set_abstraction(pk, lvl, S, radius, ns, d(xyz), d(feats), sampled=(None, d(new_xyz), d(idx)), plan=rows_plan)
     assert torch.equal(again, rows)
 
 
@@ -2155,6 +2156,91 @@ def test_gemm_kernel_choice_is_pinned(dev, case):
     from pfpp_hip import _lib
 
     call, want = _gemm_choice_cases()[case]
+    call(dev)
+    torch.cuda.synchronize()
+    assert _lib.load().pfpp_last_gemm_kernel().decode() == want
+
+
+# ----------------------------------------------------------------------------- set-abstraction stage kernel choice
+def _sa_stage_choice_cases():
+    """name -> (call(dev), expected pfpp_last_gemm_kernel()).  One pfpp_sa_train_stage launch per case, on the smallest valid inputs
+    (2 fragments x 64 points, 8 neighbourhoods each): the kernel depends on the feature width, the stage and the per-point table only."""
+    from pfpp_hip import ops, train_ops as TO
+    from pfpp_hip.packing import PW, pack_sa_first
+
+    F, N, S = 2, 64, 8
+    WIDTHS = {0: (64, 64, 128), 128: (128, 128, 256), 256: (256, 256, 512)}
+
+    def stage(D, st, table=False, sched=False):
+        def call(dev):
+            g = torch.Generator().manual_seed(D + st)
+            ns = 64 if D else 32
+            widths = WIDTHS[D]
+            rows, G = F * S * ns, F * S
+            xyz = torch.rand(F, N, 3, generator=g).to(dev)
+            feats = torch.randn(F, N, D, generator=g).to(dev) if D else None
+            new_xyz = xyz[:, :S].contiguous()
+            idx = torch.randint(0, N, (F, S, ns), generator=g, dtype=torch.int32)
+            if sched:      # the ball query's padding, as in test_sa_rows_eval_rows_equals_the_tiled_level
+                live = torch.randint(1, 33, (F, S), generator=g)
+                live = torch.where(torch.rand(F, S, generator=g) < 0.4, live, torch.randint(33, 65, (F, S), generator=g))
+                idx = torch.where(torch.arange(ns).view(1, 1, ns) < live.unsqueeze(-1), idx, idx[:, :, :1])
+            idx = idx.to(dev)
+            kin = (D + 3, widths[0], widths[1])
+            ws = []
+            for i in range(3):
+                w = torch.randn(widths[i], kin[i], generator=g) * 0.06
+                ws.append(PW((pack_sa_first(w, D) if i == 0 else w).to(dev).contiguous(), prescale=False))
+            bs = [torch.zeros(c, device=dev) for c in widths]
+            affs = [(torch.ones(c, device=dev), torch.zeros(c, device=dev)) for c in widths[:st - 1]]
+            zeros = lambda r, c: torch.zeros(r, c, device=dev)
+            kw = {}
+            if table:
+                kw["u_in"] = ops.sa_first_table(xyz, feats, ws[0], bs[0])
+            if sched:
+                kw["sched"] = ops.sa_pad_schedule(idx)
+            if D == 256 and not table:      # one rows launch per layer: this layer's raw rows out, the previous layer's in
+                if st < 3:
+                    kw["y_out"] = zeros(rows, widths[st - 1])
+                if st > 1:
+                    kw["y_in"] = zeros(rows, widths[st - 2])
+            elif D and st >= 2:             # the raw second-layer rows: written by stage 2, read by stage 3
+                kw["y_out"] = zeros(rows, widths[1])
+            if st == 3:
+                kw["out_max"], kw["out_min"] = zeros(G, widths[2]), zeros(G, widths[2])
+            ops.sa_train_stage(st, xyz, new_xyz, feats, idx, ws, bs, affs, TO.bn_stats_buffer(widths[st - 1], dev), **kw)
+        return call
+
+    wide = "sa_wide_train_kernel"
+    return {
+        "sa1_stage1": (stage(0, 1), "sa1_train_kernel<64, 64, 128, 1>"),
+        "sa1_stage2": (stage(0, 2), "sa1_train_kernel<64, 64, 128, 2>"),
+        "sa1_stage3": (stage(0, 3), "sa1_train_kernel<64, 64, 128, 3>"),
+        "sa2_stage1_grouped": (stage(128, 1), "sa2_train_kernel<128, 128, 128, 1>"),
+        "sa2_stage2_grouped": (stage(128, 2), "sa2_train_kernel<128, 128, 128, 2>"),
+        "rows8": (stage(128, 3), "sa_rows8_train_kernel<128, 256>"),
+        "rows8_schedule": (stage(128, 3, sched=True), "sa_rows8_train_kernel<128, 256>"),
+        "first_stats_128": (stage(128, 1, table=True), "sa_first_stats_kernel<128>"),
+        "first_stats_256": (stage(256, 1, table=True), "sa_first_stats_kernel<256>"),
+        "table_stage2_128": (stage(128, 2, table=True), f"{wide}<128, 2, true, false>"),
+        "table_stage2_256": (stage(256, 2, table=True), f"{wide}<256, 2, true, false>"),
+        "wide_stage1": (stage(256, 1), f"{wide}<256, 1, false, false>"),
+        "wide_stage2": (stage(256, 2), f"{wide}<256, 2, false, false>"),
+        "wide_stage3": (stage(256, 3), f"{wide}<256, 3, false, false>"),
+    }
+
+
+@pytest.mark.parametrize("case", sorted(_sa_stage_choice_cases()))
+def test_sa_stage_kernel_choice_is_pinned(dev, case):
+    """pfpp_sa_train_stage picks its kernel from the level (feature width), the stage and whether the first layer comes from the
+    per-point table; this pins the pick, one launch per launch statement.  The expected names are the template instantiations as a
+    kernel trace prints them (defaulted arguments written out): the launch statements of the commit before the choice became a function
+    with a switch behind it, and for the kernels on the benchmarked path the names in profiles/r06*_bench_train*_kernel_stats.csv.
+    (A per-case rocprofv3 trace of this list at that commit, as profiles/gemm_choice_parent_per_case.txt is for the GEMM cases, has
+    not been taken.)"""
+    from pfpp_hip import _lib
+
+    call, want = _sa_stage_choice_cases()[case]
     call(dev)
     torch.cuda.synchronize()
     assert _lib.load().pfpp_last_gemm_kernel().decode() == want

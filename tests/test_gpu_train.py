@@ -583,45 +583,58 @@ def test_padding_schedule_lists_the_two_half_neighbourhoods_first(dev):
     assert np.array_equal(sched[G + 1:2 * G + 1], cnt) and np.array_equal(sched[2 * G + 1:3 * G + 1], cnt[sched[:G]])
 
 
+def _sa_cross_check(flag):
+    """choose_sa with one thing turned off (the reference run of the chain tests); None = the product's choice.  Both runs take the
+    padding schedule wherever the chain's first layer is table-fed: 12 fragments are below the size from which it is built by default"""
+    import dataclasses
+
+    from pfpp_hip.encoder import SaPath, choose_sa
+
+    def choose(**kw):
+        p = choose_sa(**kw)
+        p = dataclasses.replace(p, pad_schedule=p.path is SaPath.TRAIN_CHAIN and p.table_first)
+        if flag == "SA_TRAIN_CHAIN" or (flag == "SA_TRAIN_WIDE" and kw["D"] == 256):
+            return dataclasses.replace(p, path=SaPath.TRAIN_LAYERWISE, table_first=False, pad_schedule=False)
+        if flag == "SA_TRAIN_UTAB":
+            return dataclasses.replace(p, table_first=False, pad_schedule=False)
+        if flag == "SA_PAD_SKIP":
+            return dataclasses.replace(p, pad_schedule=False)
+        return p
+    return choose
+
+
 @pytest.mark.parametrize("flag", ["SA_TRAIN_CHAIN", "SA_TRAIN_UTAB", "SA_TRAIN_WIDE", "SA_PAD_SKIP"])
 def test_encoder_train_chain_equals_layerwise_batchnorm(weights_sd, dev, flag):
     """train-mode set abstraction by recomputation (csrc/sa_train.hip: per-layer chain launches that write only the batch sums,
     level 2's raw second-layer rows and level 1's pooled max / min) against the layer-wise fused-BatchNorm GEMMs on the same
     fragments (F = 12 x N = 1024): same sampling, pre-quantisation features within 2e-5 of their scale, running statistics and
     counters moved identically — the two differ only in the summation order of the fp64 batch sums.
-    flag = the switch that is turned off for the comparison run: SA_TRAIN_CHAIN (everything layer-wise), SA_TRAIN_UTAB (first layer of
-    levels 2-3 as a grouped convolution instead of the per-point table: U[p] - W_xyz . centroid), SA_TRAIN_WIDE (level 3 layer-wise),
-    SA_PAD_SKIP (round 6: every neighbourhood walked as two halves instead of taking the ball query's padding — copies of row 0 — as
-    32 y_0 / 32 y_0^2 in the sums)"""
-    from pfpp_hip import config, encoder, ops
+    flag = what the comparison run's plan turns off (the names of the module switches these once were): SA_TRAIN_CHAIN (everything
+    layer-wise), SA_TRAIN_UTAB (first layer of levels 2-3 as a grouped convolution instead of the per-point table: U[p] - W_xyz .
+    centroid), SA_TRAIN_WIDE (level 3 layer-wise), SA_PAD_SKIP (round 6: every neighbourhood walked as two halves instead of taking
+    the ball query's padding — copies of row 0 — as 32 y_0 / 32 y_0^2 in the sums)"""
+    from pfpp_hip import config
     from puzzlefusion_plusplus.vqvae.model.modules.vq_vae import VQVAE
 
     gen = torch.Generator().manual_seed(77)
     pts = (torch.rand(12, 1024, 3, generator=gen) * 2 - 1) * torch.rand(12, 1, 3, generator=gen)
     res = {}
-    prev = getattr(encoder, flag)
-    prev_min = encoder.SA_PAD_SKIP_MIN
-    encoder.SA_PAD_SKIP_MIN = 0                   # 12 fragments are below the size from which the padding schedule is built by default
-    try:
-        for chain in (False, True):
-            setattr(encoder, flag, chain)
-            enc = VQVAE(config.denoiser_config())
-            enc.load_state_dict(weights_sd("vqvae"), strict=True)
-            enc = enc.to(dev).train()
-            for p in enc.parameters():
-                p.requires_grad = False
-            cap = {}
-            from pfpp_hip.encoder import pn2_encode
+    for chain in (False, True):
+        enc = VQVAE(config.denoiser_config())
+        enc.load_state_dict(weights_sd("vqvae"), strict=True)
+        enc = enc.to(dev).train()
+        for p in enc.parameters():
+            p.requires_grad = False
+        cap = {}
+        from pfpp_hip.encoder import pn2_encode
 
-            pk = enc.packed_train()
-            z_e, xyz = pn2_encode(pk, pts.to(dev), 25, cap)
-            z_e2, _ = pn2_encode(pk, pts.to(dev) * 0.5, 25)              # second pass: the running buffers move again
-            torch.cuda.synchronize()
-            res[chain] = dict(z_e=z_e.cpu(), z_e2=z_e2.cpu(), xyz=xyz.cpu(), feats={k: v.cpu() for k, v in cap.items() if k.endswith("new_points")},
-                              stats={k: v.detach().cpu().clone() for k, v in enc.state_dict().items() if "running" in k or "tracked" in k})
-    finally:
-        setattr(encoder, flag, prev)
-        encoder.SA_PAD_SKIP_MIN = prev_min
+        pk = enc.packed_train()
+        choose = _sa_cross_check(None if chain else flag)
+        z_e, xyz = pn2_encode(pk, pts.to(dev), 25, cap, choose=choose)
+        z_e2, _ = pn2_encode(pk, pts.to(dev) * 0.5, 25, choose=choose)              # second pass: the running buffers move again
+        torch.cuda.synchronize()
+        res[chain] = dict(z_e=z_e.cpu(), z_e2=z_e2.cpu(), xyz=xyz.cpu(), feats={k: v.cpu() for k, v in cap.items() if k.endswith("new_points")},
+                          stats={k: v.detach().cpu().clone() for k, v in enc.state_dict().items() if "running" in k or "tracked" in k})
     a, b = res[True], res[False]
     assert torch.equal(a["xyz"], b["xyz"])
     for k in b["feats"]:
@@ -640,8 +653,8 @@ def test_encoder_train_chain_full_size_properties(weights_sd, dev):
     fused-BatchNorm GEMMs — identical sampling, features within 2e-5 of their scale, the batch statistics the two paths hand to
     BatchNorm (running buffers after one pass) within 1e-6; a second run of the chain path reproduces its own features to 1e-6 (the only
     run-to-run freedom is the order of the fp64 atomics behind the batch sums)."""
-    from pfpp_hip import config, encoder, synthetic
-    from pfpp_hip.encoder import pn2_encode
+    from pfpp_hip import config, synthetic
+    from pfpp_hip.encoder import choose_sa, pn2_encode
     from puzzlefusion_plusplus.vqvae.model.modules.vq_vae import VQVAE
 
     data = synthetic.make_batch(0, 32, num_points=1024)
@@ -649,22 +662,17 @@ def test_encoder_train_chain_full_size_properties(weights_sd, dev):
     pts = data["part_pcs"][v].contiguous().to(dev)
     assert pts.shape[0] == 154
     res = {}
-    prev = encoder.SA_TRAIN_CHAIN
-    try:
-        for tag, chain in (("layer", False), ("chain", True), ("chain2", True)):
-            encoder.SA_TRAIN_CHAIN = chain
-            enc = VQVAE(config.denoiser_config())
-            enc.load_state_dict(weights_sd("vqvae"), strict=True)
-            enc = enc.to(dev).train()
-            for p in enc.parameters():
-                p.requires_grad = False
-            cap = {}
-            z_e, xyz = pn2_encode(enc.packed_train(), pts, 25, cap)
-            torch.cuda.synchronize()
-            res[tag] = dict(z_e=z_e.cpu(), xyz=xyz.cpu(), f2=cap["sa2.new_points"].cpu(), f1=cap["sa1.new_points"].cpu(),
-                            stats={k: t.detach().cpu().clone() for k, t in enc.state_dict().items() if "running" in k})
-    finally:
-        encoder.SA_TRAIN_CHAIN = prev
+    for tag, chain in (("layer", False), ("chain", True), ("chain2", True)):
+        enc = VQVAE(config.denoiser_config())
+        enc.load_state_dict(weights_sd("vqvae"), strict=True)
+        enc = enc.to(dev).train()
+        for p in enc.parameters():
+            p.requires_grad = False
+        cap = {}
+        z_e, xyz = pn2_encode(enc.packed_train(), pts, 25, cap, choose=choose_sa if chain else _sa_cross_check("SA_TRAIN_CHAIN"))
+        torch.cuda.synchronize()
+        res[tag] = dict(z_e=z_e.cpu(), xyz=xyz.cpu(), f2=cap["sa2.new_points"].cpu(), f1=cap["sa1.new_points"].cpu(),
+                        stats={k: t.detach().cpu().clone() for k, t in enc.state_dict().items() if "running" in k})
     a, b, c = res["chain"], res["layer"], res["chain2"]
     assert torch.equal(a["xyz"], b["xyz"])
     for k in ("f1", "f2", "z_e"):

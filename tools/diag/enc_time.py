@@ -1,5 +1,5 @@
 """the frozen encoder in train mode alone (BASELINE configs[1] batch): wall time per pass on the whole chip and the per-launch
-table of the set-abstraction stages (ops.GEMM_TRACE), for PFPP_SA_TRAIN_WIDE / PFPP_SA_TRAIN_CHAIN A/Bs"""
+table of the set-abstraction stages (ops.GEMM_TRACE): the kernel each stage launched (pfpp_last_gemm_kernel) and its time"""
 import sys, time, collections
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[2]
