@@ -749,7 +749,15 @@ int pfpp_dropout_layernorm(const float* y, const float* res, float* h_out, float
  * dqkv [rows, 3*H*dh] receives (dq | dk | dv) of softmax(q.k^T * scale) v.
  * pfpp_attn_dense_train: pfpp_attn_dense that also writes lse[row, h] = log sum_j exp(s_ij) (needed by
  * the backward).  pfpp_attn_dense_bwd: two passes without atomics — dq per query block, dk/dv per key
- * block, both recomputing the probabilities from q, k and lse.                                       */
+ * block, both recomputing the probabilities from q, k and lse.
+ * Rows outside every sequence / fragment are not written; masked keys receive dk = dv = 0; a sequence
+ * without a valid key is outside the contract.  key_valid rows are kv_stride >= max(seq_len) bytes apart.
+ * Range of dout.  The exact-fp32 kernels (key mask given, or dim_head 32) have fp32's range.  The split-f16
+ * kernels (dense: dim_head 64 without a key mask; block-diagonal) lift dout by 2^12 and
+ * dS = P (dout . v - D) scale by 2^14 times a power of two chosen per query row from max|dout row| (1 for
+ * |dout| in [1.2e-4, 0.125)) before an fp16 hi / lo split: supported is |dout| < 16; from there on the
+ * result is non-finite (inf / NaN), never a finite wrong value.  Downwards the 2e-5 accuracy of dqkv holds
+ * to |dout| ~ 1e-6 and degrades gradually below ~1e-8.  DESIGN.md 4.1.                                  */
 int pfpp_attn_blockdiag_bwd(const float* qkv, const float* dout, float* dqkv, int64_t n_frag,
                             int64_t L, int64_t H, int64_t dh, float scale, pfpp_stream_t stream);
 int pfpp_attn_dense_train(const float* qkv, float* out, float* lse, const int32_t* seq_off,

@@ -377,6 +377,27 @@ __device__ __forceinline__ void ab_split(float x, _Float16& hi, _Float16& lo) {
   lo = (_Float16)(x - (float)h);
 }
 
+// dS = P (dP - D) scale is linear in a query's dO row, and its fixed 2^14 lift only fits rows whose gradients have the size the
+// training step produces: at |dO| ~ 15 the lifted dS passes the fp16 range (inf, then NaN), at |dO| ~ 1e-6 it falls to the fp16
+// subnormals (12 bits left).  So the lift of a query row's dS gets a further power of two a from M = 2^12 max|dO row|: a = 1 while
+// M is in [2^-1, 2^9) (|dO| from 1.2e-4 to 0.125: every bit as without it), above that the a < 1 that brings M a into [2^8, 2^9), below
+// it a = 2^min(cap, ...) that brings M a up to 2^-1.  Where the sum runs over the keys of one query (dq) the result is divided by a
+// again; where it runs over queries (dk) the other operand, the transposed q row, carries 1 / a — exact in fp16 up to |q| < 511 a,
+// but its low half loses bits as a grows, hence the smaller cap there.
+__device__ __forceinline__ float ab_row_scale(float M, int cap) {
+  if (!(M < 65520.0f) || (M >= 0.5f && M < 512.0f)) return 1.0f;
+  const int e = (int)((__float_as_uint(M) >> 23) & 0xffu) - 127;
+  const int k = e >= 9 ? 8 - e : min(-1 - e, cap);
+  return __uint_as_float((unsigned)(127 + k) << 23);
+}
+constexpr int AB_CAP_DQ = 12, AB_CAP_DK = 7;
+
+__device__ __forceinline__ float ab_absmax8(const ab_half8 h, float m) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf((float)h[e]));
+  return m;
+}
+
 // 8 consecutive floats (x scale) -> hi / lo operand fragment
 __device__ __forceinline__ void ab_frag8(const float* p, float sc, ab_half8& hi, ab_half8& lo) {
   const float4 a = *reinterpret_cast<const float4*>(p);
@@ -433,7 +454,9 @@ __device__ __forceinline__ int ab_toff(int dim, int row) { return dim * AB_LDT +
 
 // one float4 of a [row r][dims c4*4..] tile (thread idx = r*16 + c4) -> row planes (8-byte store) and, if th, transposed
 // planes: lanes r and r+1 (16 apart) swap halves first, so each writes TWO rows of two dims as 4-byte words
-__device__ __forceinline__ void ab_store4(const float4 v, float sc, int r, int c4, _Float16* rh, _Float16* rl, _Float16* th, _Float16* tl) {
+// (tsc: a power of two the transposed planes alone are multiplied by — exact on both halves)
+__device__ __forceinline__ void ab_store4(const float4 v, float sc, int r, int c4, _Float16* rh, _Float16* rl, _Float16* th, _Float16* tl,
+                                          float tsc = 1.0f) {
   const float x[4] = {v.x * sc, v.y * sc, v.z * sc, v.w * sc};
   ab_half4 h4, l4;
 #pragma unroll
@@ -446,7 +469,9 @@ __device__ __forceinline__ void ab_store4(const float4 v, float sc, int r, int c
   *reinterpret_cast<ab_half4*>(rl + r * AB_LDR + c4 * 4) = l4;
   if (th) {
     union { ab_half4 h; int2 i; } uh, ul;
-    uh.h = h4; ul.h = l4;
+    const _Float16 ts = (_Float16)tsc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { uh.h[j] = h4[j] * ts; ul.h[j] = l4[j] * ts; }
     const bool odd = r & 1;
     // even rows keep dims 0,1 (word .x) and send dims 2,3 (.y); odd rows keep dims 2,3 and send dims 0,1
     const int keep_h = odd ? uh.i.y : uh.i.x, send_h = odd ? uh.i.x : uh.i.y;
@@ -470,7 +495,7 @@ __device__ __forceinline__ void ab_store4(const float4 v, float sc, int r, int c
 typedef _Float16 AbRowTile[KT * AB_LDR];       // [row][dim] planes of a 32-row tile
 typedef _Float16 AbTrTile[64 * AB_LDT];        // [dim][row] planes
 constexpr int AB_DQ_SMEM = 8 * (int)sizeof(AbRowTile) + 4 * (int)sizeof(AbTrTile);
-constexpr int AB_DKV_SMEM = 8 * (int)sizeof(AbRowTile) + 8 * (int)sizeof(AbTrTile) + 4 * KT * (int)sizeof(float);
+constexpr int AB_DKV_SMEM = 8 * (int)sizeof(AbRowTile) + 8 * (int)sizeof(AbTrTile) + 6 * KT * (int)sizeof(float);
 
 __device__ __forceinline__ void ab_dq_f16_body(
     char* smem, const int blk, const float* __restrict__ qkv, const float* __restrict__ out, const float* __restrict__ dout,
@@ -524,6 +549,11 @@ __device__ __forceinline__ void ab_dq_f16_body(
     ab_frag8(base + (int64_t)q_cl * ld + c * 16 + lhi * 8, 1.0f, qh[c], ql[c]);
     ab_frag8(dout + (row0 + q_cl) * (int64_t)C + h * DH + c * 16 + lhi * 8, AB_GS, gh[c], gl[c]);
   }
+  float gmax = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) gmax = ab_absmax8(gh[c], gmax);
+  const float aq = ab_row_scale(fmaxf(gmax, __shfl_xor(gmax, 32)), AB_CAP_DQ);      // this lane's query (ab_row_scale)
+  const float ds_lift = (scale * AB_DS) * aq;
   f32x16 dq_acc[2];
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
@@ -550,14 +580,17 @@ __device__ __forceinline__ void ab_dq_f16_body(
     for (int it = 0; it < F4; ++it) {
       const int idx = tid + 256 * it;
       const int r = idx / (DH / 4), c4 = idx % (DH / 4);
-      // rows past the end of the sequence are staged as zero keys: S = 0 -> a finite P, and K^T . dS^T gets nothing from them,
-      // so the tile loop needs no per-entry key mask
+      // rows past the end of the sequence are staged as zero keys, so K^T . dS^T gets nothing from them as long as their dS is
+      // finite.  That is NOT given by S = 0: their "P" is exp(-lse_q), no probability, and with a negative enough lse the lifted
+      // dS leaves the fp16 range (0 . inf = NaN into the whole dq row), so the last tile sets their dS to zero (below); the
+      // other tiles hold real keys only and need no per-entry mask
       ab_store4(rk[it], tile_k0 + r < T ? 1.0f : 0.0f, r, c4, Kh[buf], Kl[buf], Kth[buf], Ktl[buf]);
       ab_store4(rv[it], 1.0f, r, c4, Vh[buf], Vl[buf], nullptr, nullptr);
     }
   };
 
   const int nt = (T + KT - 1) / KT;
+  const int tail = T & (KT - 1);              // keys of the last tile that exist (0: all of them)
   load_tile(0);
   store_tile(0);
   __syncthreads();
@@ -578,7 +611,12 @@ __device__ __forceinline__ void ab_dq_f16_body(
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const float pv = __builtin_amdgcn_exp2f(fmaf(s[e], sc2, -lse_q));
-      s[e] = pv * (dp[e] * (1.0f / AB_GS) - Dq) * (scale * AB_DS);      // dS^T * 2^14
+      s[e] = pv * (dp[e] * (1.0f / AB_GS) - Dq) * ds_lift;              // dS^T * 2^14 a
+    }
+    if (tail != 0 && t == nt - 1) {           // wave-uniform: an exact zero dS for the keys past the end (a select, whatever was there)
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        if ((e & 3) + 8 * (e >> 2) + 4 * lhi >= tail) s[e] = 0.0f;
     }
     ab_half8 sh[2], sl[2];
     ab_acc_to_fragments(s, lhi, sh, sl);
@@ -595,7 +633,7 @@ __device__ __forceinline__ void ab_dq_f16_body(
 
   if (q_row < T) {
     const int64_t d0 = (row0 + q_row) * ld + h * DH + lhi * 4;
-    constexpr float inv = 1.0f / AB_DS;
+    const float inv = (1.0f / AB_DS) / aq;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -634,6 +672,7 @@ __device__ __forceinline__ void ab_dkv_f16_body(
   typedef float AbVec[KT];
   AbVec* Ls = reinterpret_cast<AbVec*>(Gtl + 2);
   AbVec* Ds = Ls + 2;
+  AbVec* As = Ds + 2;          // ab_row_scale of the tile's query rows
 
   const int b = blockIdx.z, h = blockIdx.y;
   const int T = seq_len[b];
@@ -691,8 +730,14 @@ __device__ __forceinline__ void ab_dkv_f16_body(
     for (int it = 0; it < F4; ++it) {
       const int idx = tid + 256 * it;
       const int r = idx / (DH / 4), c4 = idx % (DH / 4);
-      ab_store4(rq[it], 1.0f, r, c4, Qh[buf], Ql[buf], Qth[buf], Qtl[buf]);
+      // the 16 lanes that hold row r: its max|dO| -> a (dS of the row is lifted by a more, q^T carries 1 / a for the sum over queries)
+      float gm = fmaxf(fmaxf(fabsf(rg[it].x), fabsf(rg[it].y)), fmaxf(fabsf(rg[it].z), fabsf(rg[it].w)));
+      gm = fmaxf(gm, __shfl_xor(gm, 1)); gm = fmaxf(gm, __shfl_xor(gm, 2));
+      gm = fmaxf(gm, __shfl_xor(gm, 4)); gm = fmaxf(gm, __shfl_xor(gm, 8));
+      const float a = ab_row_scale(gm * AB_GS, AB_CAP_DK);
+      ab_store4(rq[it], 1.0f, r, c4, Qh[buf], Ql[buf], Qth[buf], Qtl[buf], 1.0f / a);
       ab_store4(rg[it], AB_GS, r, c4, Gh[buf], Gl[buf], Gth[buf], Gtl[buf]);
+      if (c4 == 0) As[buf][r] = a;
     }
     if (tid < KT) { Ls[buf][tid] = rl_ok ? rl * LOG2E : __builtin_huge_valf(); Ds[buf][tid] = rd; }
   };
@@ -730,13 +775,14 @@ __device__ __forceinline__ void ab_dkv_f16_body(
     for (int g = 0; g < 4; ++g) {
       const float4 l4 = *reinterpret_cast<const float4*>(&Ls[buf][8 * g + 4 * lhi]);     // rows (e & 3) + 8 (e >> 2) + 4 lhi
       const float4 d4 = *reinterpret_cast<const float4*>(&Ds[buf][8 * g + 4 * lhi]);
-      const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, dq_[4] = {d4.x, d4.y, d4.z, d4.w};
+      const float4 a4 = *reinterpret_cast<const float4*>(&As[buf][8 * g + 4 * lhi]);
+      const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, dq_[4] = {d4.x, d4.y, d4.z, d4.w}, aj[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int e = 4 * g + j;
         const float pv = __builtin_amdgcn_exp2f(fmaf(s[e], sc2, -lq[j]));
         s[e] = pv;
-        dp[e] = pv * (dp[e] * (1.0f / AB_GS) - dq_[j]) * (scale * AB_DS);     // dS * 2^14
+        dp[e] = pv * (dp[e] * (1.0f / AB_GS) - dq_[j]) * ((scale * AB_DS) * aj[j]);     // dS * 2^14 a
       }
     }
     AB_STAMP_NOWAIT(3);
@@ -1085,12 +1131,28 @@ __global__ __launch_bounds__(64) void attn_blockdiag_bwd_f16_kernel(const float*
       ab_frag8(qrow + 2 * C + c * 16, 1.0f, vh[c], vl[c]);
       ab_frag8(grow + c * 16, AB_GS, gh[c], gl[c]);
       const int off = l31 * BDF_LD + c * 16 + lhi * 8;
-      *reinterpret_cast<ab_half8*>(&planes[0][0][off]) = qh[c];
-      *reinterpret_cast<ab_half8*>(&planes[0][1][off]) = ql[c];
       *reinterpret_cast<ab_half8*>(&planes[1][0][off]) = kh[c];
       *reinterpret_cast<ab_half8*>(&planes[1][1][off]) = kl[c];
       *reinterpret_cast<ab_half8*>(&planes[2][0][off]) = gh[c];
       *reinterpret_cast<ab_half8*>(&planes[2][1][off]) = gl[c];
+    }
+  }
+  // this lane's row as a query: the further lift of its dS (ab_row_scale); the q plane, read only by dK^T = Q^T . dS, carries 1 / a
+  float gmax = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) gmax = ab_absmax8(gh[c], gmax);
+  gmax = fmaxf(gmax, __shfl_xor(gmax, 32));
+  const float a_dq = ab_row_scale(gmax, AB_CAP_DQ), a_dk = ab_row_scale(gmax, AB_CAP_DK);
+  {
+    const _Float16 qs = (_Float16)(1.0f / a_dk);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int off = l31 * BDF_LD + c * 16 + lhi * 8;
+      ab_half8 sh, sl;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { sh[e] = qh[c][e] * qs; sl[e] = ql[c][e] * qs; }
+      *reinterpret_cast<ab_half8*>(&planes[0][0][off]) = sh;
+      *reinterpret_cast<ab_half8*>(&planes[0][1][off]) = sl;
     }
   }
   // transposing reads: lane (q4 = lane >> 4, j = lane & 15) supplies token row 8 (q4 >> 1) + (j >> 2), dims 16 (q4 & 1) + 4 (j & 3)
@@ -1160,8 +1222,8 @@ __global__ __launch_bounds__(64) void attn_blockdiag_bwd_f16_kernel(const float*
   }
   dsum += __shfl_xor(dsum, 32);            // D[query]
 #pragma unroll
-  for (int e = 0; e < 16; ++e) dpt[e] = st[e] * (dpt[e] - dsum) * (scale * AB_DS);      // dS^T * 2^14 (0 at masked keys)
-  second(lds_k, dpt, 1.0f / AB_DS, gb);                                        // dQ^T = K^T . dS^T  -> dq rows
+  for (int e = 0; e < 16; ++e) dpt[e] = st[e] * (dpt[e] - dsum) * ((scale * AB_DS) * a_dq);      // dS^T * 2^14 a (0 at masked keys)
+  second(lds_k, dpt, (1.0f / AB_DS) / a_dq, gb);                                        // dQ^T = K^T . dS^T  -> dq rows
 
   // ---- keys on lanes ----
   f32x16 sk = prod(qh, ql, kh, kl);            // sk[e]: query (e&3)+8*(e>>2)+4*lhi, key l31
@@ -1169,11 +1231,11 @@ __global__ __launch_bounds__(64) void attn_blockdiag_bwd_f16_kernel(const float*
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int qi = (e & 3) + 8 * (e >> 2) + 4 * lhi;
-    const float m_q = __shfl(mx, qi), i_q = __shfl(inv, qi), d_q = __shfl(dsum, qi);
+    const float m_q = __shfl(mx, qi), i_q = __shfl(inv, qi), d_q = __shfl(dsum, qi), a_q = __shfl(a_dk, qi);
     const float ev = __expf(sk[e] * scale - m_q) * i_q;
     const float pv = qi < L ? ev : 0.0f;                                        // queries >= L do not exist
     sk[e] = pv;
-    dp[e] = pv * (dp[e] * (1.0f / AB_GS) - d_q) * (scale * AB_DS);              // dS * 2^14
+    dp[e] = pv * (dp[e] * (1.0f / AB_GS) - d_q) * ((scale * AB_DS) * a_q);      // dS * 2^14 a
   }
   second(lds_g, sk, 1.0f / AB_GS, gb + 2 * C);                                 // dV^T = dO^T . P   -> dv rows
   second(lds_q, dp, 1.0f / AB_DS, gb + C);                                     // dK^T = Q^T . dS   -> dk rows

@@ -62,6 +62,20 @@ def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _key_valid_stride(t: Optional[torch.Tensor]) -> int:
+    """row stride (bytes) of a key mask for the dense attention kernels: uint8 [..., >= longest sequence], contiguous, or a 2-d column slice
+    of a wider tensor (unit column stride, rows further apart than they are long); 0 for None"""
+    if t is None:
+        return 0
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+        raise ValueError("key_valid: expected a uint8 tensor on the GPU")
+    if t.is_contiguous():
+        return t.shape[-1]
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return t.stride(0)
+    raise ValueError("key_valid: must be contiguous or a column slice of a contiguous 2-d tensor")
+
+
 # --------------------------------------------------------------------------- SE(3)
 def se3_rotate_gather(part_pcs: torch.Tensor, pose: torch.Tensor, slot: torch.Tensor) -> torch.Tensor:
     """part_pcs [n_slots,N,3], pose [n_slots,7], slot int32 [F] -> [F,N,3] (include/pfpp.h a1)"""
@@ -983,10 +997,7 @@ def attn_dense(qkv: torch.Tensor, seq_off: torch.Tensor, seq_len: torch.Tensor, 
     rows, w = qkv.shape
     if w != 3 * H * dh:
         raise ValueError("attn_dense: qkv must be [rows, 3*H*dh]")
-    kv_stride = 0
-    if key_valid_u8 is not None:
-        _chk(key_valid_u8, torch.uint8, "key_valid")
-        kv_stride = key_valid_u8.shape[-1]
+    kv_stride = _key_valid_stride(key_valid_u8)
     if isinstance(out, SplitAct):
         check(_lib.load().pfpp_attn_dense_split(_ptr(qkv), _ptr(out.hi), _ptr(out.lo), _ptr(seq_off), _ptr(seq_len),
                                                 _ptr(key_valid_u8), kv_stride, seq_off.numel(), max_len, H, dh, scale,

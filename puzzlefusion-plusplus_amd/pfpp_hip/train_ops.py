@@ -260,17 +260,16 @@ def attn_blockdiag_bwd(qkv: torch.Tensor, dout: torch.Tensor, n_frag: int, L: in
 
 def attn_dense_train(qkv: torch.Tensor, seq_off: torch.Tensor, seq_len: torch.Tensor, max_len: int, H: int, dh: int,
                      scale: float, key_valid: Optional[torch.Tensor] = None,
-                     out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """pfpp_attn_dense that also returns lse [rows, H] for the backward"""
+                     out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pfpp_attn_dense that also returns lse [rows, H] for the backward.  Rows outside every sequence are not written."""
     _chk(qkv, _f32, "qkv"); _chk(seq_off, torch.int32, "seq_off"); _chk(seq_len, torch.int32, "seq_len")
     rows = qkv.shape[0]
     if out is None:
         out = torch.empty((rows, H * dh), dtype=_f32, device=qkv.device)
-    lse = torch.empty((rows, H), dtype=_f32, device=qkv.device)
-    kvs = 0
-    if key_valid is not None:
-        _chk(key_valid, torch.uint8, "key_valid")
-        kvs = key_valid.stride(0)
+    if lse is None:
+        lse = torch.empty((rows, H), dtype=_f32, device=qkv.device)
+    _chk(out, _f32, "out"); _chk(lse, _f32, "lse")
+    kvs = ops._key_valid_stride(key_valid)
     check(_lib.load().pfpp_attn_dense_train(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(seq_off), _ptr(seq_len), _ptr(key_valid),
                                             kvs, seq_off.numel(), max_len, H, dh, scale, _stream()), "pfpp_attn_dense_train")
     return out, lse
@@ -279,17 +278,17 @@ def attn_dense_train(qkv: torch.Tensor, seq_off: torch.Tensor, seq_len: torch.Te
 def attn_dense_bwd(qkv: torch.Tensor, out_fwd: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, seq_off: torch.Tensor,
                    seq_len: torch.Tensor, max_len: int, H: int, dh: int, scale: float,
                    key_valid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                   aux_stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+                   aux_stream: Optional[torch.cuda.Stream] = None, dvec: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dqkv of the dense (ragged, key-masked) attention.  With `aux_stream` the dk/dv pass runs there while dq runs on the
-    current stream (both after the small D = rowsum(dout . out) kernel); the current stream waits for both before returning."""
+    current stream (both after the small D = rowsum(dout . out) kernel); the current stream waits for both before returning.
+    dvec [rows, H]: the workspace that receives D (allocated when None).  Rows outside every sequence are not written."""
     _chk(qkv, _f32, "qkv"); _chk(out_fwd, _f32, "out_fwd"); _chk(dout, _f32, "dout"); _chk(lse, _f32, "lse")
     if out is None:
         out = torch.empty_like(qkv)
-    dvec = torch.empty_like(lse)
-    kvs = 0
-    if key_valid is not None:
-        _chk(key_valid, torch.uint8, "key_valid")
-        kvs = key_valid.stride(0)
+    if dvec is None:
+        dvec = torch.empty_like(lse)
+    _chk(out, _f32, "out"); _chk(dvec, _f32, "dvec")
+    kvs = ops._key_valid_stride(key_valid)
     if aux_stream is not None:
         def part(bits):
             check(_lib.load().pfpp_attn_dense_bwd_parts(_ptr(qkv), _ptr(out_fwd), _ptr(dout), _ptr(lse), _ptr(dvec), _ptr(out),
