@@ -1256,6 +1256,40 @@ int pfpp_ragged_interp(const float* xyz1, const float* xyz2, const int32_t* idx,
                        const float* points1, int64_t D1, int64_t N, int64_t S, float* out, int64_t ldo, float* weights,
                        pfpp_stream_t stream);
 
+/* ---- matcher middle: point-transformer and cross-attention layers (Jigsaw_matching/model/jigsaw/attention_layer.py; csrc/matching_tf.hip)
+ * Layout as above: the points of all pieces of all puzzles flat, piece_off int64 [P + 1].
+ * pfpp_feat_knn (knn_and_group :136-139: knn(x, x, k, batch_x, batch_x) + to_dense_batch(fill_value = N, max_num_nodes = k)): for every
+ * row of feats [N, C] (row stride ld floats, so a third of a packed projection is searched in place) the min(K, n_piece) nearest
+ * rows OF ITS PIECE in feature space as global indices int32 [N, K], ascending by key, ties to the lower index; the remaining slots
+ * hold N.  The key is d = 0; for c = 0 .. C - 1 in order: t = a_c - b_c; d = d + t t, in fp32 without contraction, compared as (bits
+ * of d, index).  C = 128, K = 16.  max_n = the largest piece as the caller states it: the entry refuses more than 8192 (the limit
+ * of the encoder in front, pfpp_ragged_fps) and the kernel itself does not depend on it.  The launch has ceil(N / 64) + P workgroups
+ * and each finds its piece by a linear walk over piece_off: meant for the hundreds of pieces of a batch of puzzles (P <= 65536).
+ * pfpp_ptf_aggregate (PointTransformerLayer.forward :206-224 behind the projections and the two searches): per point i and slot t
+ *   p_r = linear_p(xyz[idx_k[i, t]] - xyz[i]),  r = (k[idx_k[i, t]] - q[i]) + p_r,  w = softmax_t(linear_w(r)),
+ *   out[i, 16 s + c] = sum_t (v[idx_v[i, t], 16 s + c] + p_r[i, t, 16 s + c]) w[i, t, c];
+ * an index outside [0, N) is the reference's appended row: zero features and a zero offset (it stays in the softmax).  q, k, v
+ * [N, C] share the row stride ld.  weights: PFPP_PTF_WEIGHT_FLOATS floats, BatchNorm in eval mode as (scale, shift) behind its
+ * linear layer, at the offsets  0 linear_p.0.weight [3, 3] | 12 its BatchNorm scale [3] | 16 shift [3] (with the bias) | 20
+ * linear_p.3.weight [128, 3] | 404 linear_p.3.bias | 532 linear_w.0 scale [128] | 660 shift [128] | 788 linear_w.2.weight [16, 128] |
+ * 2836 linear_w.3 scale [16] | 2852 shift [16] (with the bias of linear_w.2) | 2868 linear_w.5.weight [16, 16] | 3124 linear_w.5.bias.
+ * All products are fp32 FMAs; nothing of size [N, K, .] is written.  C = 128, K = 16.
+ * pfpp_attn_rows16 (ScaledDotProductAttention :17-24 inside MultiHeadAttention :47-69, mask = None): pfpp_attn_dense's arguments
+ * without a key mask for dh = 16: softmax((q scale) k^T) v per (sequence, head) from qkv [rows, 3 H 16] (q | k | v), out [rows, H 16];
+ * online softmax, fp32 FMAs, one arithmetic whatever the thread's attention mode or the environment says.  Sequences of any length.
+ * pfpp_layernorm128 (nn.LayerNorm(d_model, eps=1e-6) of MultiHeadAttention :45, :73 and PositionwiseFeedForward :85, :95): out[r] =
+ * (x[r] - mean) / sqrt(mean((x[r] - mean)^2) + eps) gamma + beta over rows of C = 128 channels, the width pfpp_layernorm (256, 512,
+ * 1024) does not cover; out may alias x.                                                                                          */
+#define PFPP_PTF_WEIGHT_FLOATS 3140
+int pfpp_feat_knn(const float* feats, int64_t ld, const int64_t* piece_off, int64_t P, int64_t N, int64_t C, int64_t K, int64_t max_n,
+                  int32_t* idx, pfpp_stream_t stream);
+int pfpp_ptf_aggregate(const float* q, const float* k, const float* v, int64_t ld, const float* xyz, const int32_t* idx_k,
+                       const int32_t* idx_v, const float* weights, int64_t N, int64_t C, int64_t K, float* out, pfpp_stream_t stream);
+int pfpp_attn_rows16(const float* qkv, float* out, const int32_t* seq_off, const int32_t* seq_len, int64_t n_seq, int64_t max_len,
+                     int64_t H, int64_t dh, float scale, pfpp_stream_t stream);
+int pfpp_layernorm128(const float* x, const float* gamma, const float* beta, float* out, int64_t rows, int64_t C, float eps,
+                      pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

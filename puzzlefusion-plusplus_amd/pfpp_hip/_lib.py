@@ -341,6 +341,10 @@ SIGNATURES = {
     "pfpp_ragged_knn": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p],
     "pfpp_ragged_group": [_p, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p],
     "pfpp_ragged_interp": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _p],
+    "pfpp_feat_knn": [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _p],
+    "pfpp_ptf_aggregate": [_p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p],
+    "pfpp_attn_rows16": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
+    "pfpp_layernorm128": [_p, _p, _p, _p, _i64, _i64, _f32, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),

@@ -1,10 +1,13 @@
-"""matching_data from per-point descriptors on one GPU — the back half of the reference's matcher (Jigsaw_matching/, test run)
+"""matching_data from point clouds or from per-point descriptors on one GPU — the reference's matcher (Jigsaw_matching/, test run)
 
-    python -m pfpp_hip.generate_matching_data --features DIR --checkpoint CKPT --out DIR [--batch-size 16] [--gemm f32|f16x3]
+    python -m pfpp_hip.generate_matching_data (--points DIR | --features DIR) --checkpoint CKPT --out DIR [--batch-size 16]
+                                              [--gemm f32|f16x3] [--seed S]
 
-reads one DIR/<data_id>.npz per puzzle (part_feats float32 [N_sum, 128], gt_pcs float32 [N_sum, 3], n_pcs int64 [P], part_valids
-[P]: the seam the descriptor network feeds), runs pfpp_hip.matching.MatchingHead in batches and writes
-OUT/<data_id>.npz through pfpp_hip.io.save_matching_data.  A file that exists is left alone and its puzzle is not computed."""
+--points reads one DIR/<data_id>.npz per puzzle (part_pcs float32 [N_sum, 3]: the pieces' points as the matcher sees them, gt_pcs
+float32 [N_sum, 3], n_pcs int64 [P], part_valids [P]) and runs pfpp_hip.matching.DescriptorNetwork (encoder, tf_self1, tf_cross1) in
+front of the head; --features reads the descriptors themselves (part_feats float32 [N_sum, 128] in place of part_pcs: the seam
+between the two).  Either way pfpp_hip.matching.MatchingHead runs in batches and OUT/<data_id>.npz is written
+through pfpp_hip.io.save_matching_data.  A file that exists is left alone and its puzzle is not computed."""
 from __future__ import annotations
 
 import argparse
@@ -14,6 +17,7 @@ import time
 from typing import List, Optional
 
 FEATURE_KEYS = ("part_feats", "gt_pcs", "n_pcs", "part_valids")
+POINT_KEYS = ("part_pcs", "gt_pcs", "n_pcs", "part_valids")
 
 
 def list_puzzles(features: str, out: str):
@@ -29,36 +33,42 @@ def list_puzzles(features: str, out: str):
     return sorted(todo), sorted(skipped)
 
 
-def load_features(features: str, data_id: int):
+def load_features(features: str, data_id: int, points: bool = False):
+    """one puzzle's file: the descriptors (part_feats [N_sum, 128]) or, with points, the point clouds (part_pcs [N_sum, 3])"""
     import numpy as np
 
+    keys, first, width = (POINT_KEYS, "part_pcs", 3) if points else (FEATURE_KEYS, "part_feats", 128)
     path = os.path.join(features, f"{data_id}.npz")
     with np.load(path) as d:
-        missing = [k for k in FEATURE_KEYS if k not in d.files]
+        missing = [k for k in keys if k not in d.files]
         if missing:
             raise KeyError(f"{path}: missing entries {missing}")
-        x = {k: d[k] for k in FEATURE_KEYS}
+        x = {k: d[k] for k in keys}
     n = int(np.asarray(x["n_pcs"]).sum())
-    if x["part_feats"].shape != (n, 128) or x["gt_pcs"].shape != (n, 3) or x["n_pcs"].shape != x["part_valids"].shape:
-        raise ValueError(f"{path}: part_feats {x['part_feats'].shape}, gt_pcs {x['gt_pcs'].shape} do not match n_pcs (sum {n})")
+    if x[first].shape != (n, width) or x["gt_pcs"].shape != (n, 3) or x["n_pcs"].shape != x["part_valids"].shape:
+        raise ValueError(f"{path}: {first} {x[first].shape}, gt_pcs {x['gt_pcs'].shape} do not match n_pcs (sum {n})")
     return x
 
 
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m pfpp_hip.generate_matching_data", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--features", required=True, help="directory of <data_id>.npz descriptor files")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--points", help="directory of <data_id>.npz point-cloud files (the descriptor network runs in front of the head)")
+    src.add_argument("--features", help="directory of <data_id>.npz descriptor files")
     ap.add_argument("--checkpoint", required=True, help="Jigsaw checkpoint (Lightning file or bare state_dict)")
     ap.add_argument("--out", required=True, help="matching_data directory")
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--gemm", choices=("f32", "f16x3"), default="f32")
+    ap.add_argument("--seed", type=int, default=0, help="--points: seed of the encoder's sampling starts (the reference draws them at random)")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be at least 1")
-    if not os.path.isdir(args.features):
-        ap.error(f"--features {args.features}: not a directory")
+    source, flag = (args.points, "--points") if args.points is not None else (args.features, "--features")
+    if not os.path.isdir(source):
+        ap.error(f"{flag} {source}: not a directory")
     if not os.path.isfile(args.checkpoint):
         ap.error(f"--checkpoint {args.checkpoint}: no such file")
-    todo, skipped = list_puzzles(args.features, args.out)
+    todo, skipped = list_puzzles(source, args.out)
     if skipped:
         print(f"{len(skipped)} puzzles already in {args.out}: left alone", flush=True)
     if not todo:
@@ -71,18 +81,23 @@ def main(argv: Optional[List[str]] = None) -> int:
     if not torch.cuda.is_available():
         print("generate_matching_data: no GPU: the matching kernels run on the GPU only", file=sys.stderr)
         return 2
-    from pfpp_hip.matching import MatchingHead, match_edges, write_matching_data
+    from pfpp_hip.matching import DescriptorNetwork, MatchingHead, match_edges, write_matching_data
 
     head = MatchingHead.from_checkpoint(args.checkpoint, gemm_mode=args.gemm).cuda()
+    net = DescriptorNetwork.from_checkpoint(args.checkpoint, gemm_mode=args.gemm).cuda() if args.points is not None else None
     t0, n, host = time.perf_counter(), 0, 0.0
     for i in range(0, len(todo), args.batch_size):
         ids = todo[i:i + args.batch_size]
-        items = [load_features(args.features, d) for d in ids]
+        items = [load_features(source, d, points=net is not None) for d in ids]
         P = max(x["n_pcs"].shape[0] for x in items)
         pad = lambda a: np.concatenate([np.asarray(a).reshape(-1), np.zeros(P - a.shape[0], dtype=a.dtype)])
-        out = head([torch.from_numpy(np.ascontiguousarray(x["part_feats"], dtype=np.float32)).cuda() for x in items],
-                   np.stack([pad(x["n_pcs"].astype(np.int64)) for x in items]), np.stack([pad(x["part_valids"].astype(np.float32)) for x in items]),
-                   dense_perm=False)
+        n_pcs, valids = np.stack([pad(x["n_pcs"].astype(np.int64)) for x in items]), np.stack([pad(x["part_valids"].astype(np.float32)) for x in items])
+        if net is not None:          # descriptors of the whole batch, flat, as the head takes them
+            feats = net([torch.from_numpy(np.ascontiguousarray(x["part_pcs"], dtype=np.float32)).cuda() for x in items], n_pcs, valids,
+                        seed=args.seed + i)
+        else:
+            feats = [torch.from_numpy(np.ascontiguousarray(x["part_feats"], dtype=np.float32)).cuda() for x in items]
+        out = head(feats, n_pcs, valids, dense_perm=False)
         host += out.timings["host_assignment_s"]
         nc = out.n_critical_pcs.cpu().numpy()
         for b, (d, x) in enumerate(zip(ids, items)):

@@ -445,3 +445,57 @@ class MatchingHead(nn.Module):
         return HeadOutput([t.reshape(-1, 1) for t in torch.split(logits, sizes)], list(torch.split(labels.to(torch.int64), sizes)),
                           list(torch.split(crit, sizes)), n_crit.reshape(B, P), ds_list, perms,
                           {"wall_s": wall, "host_assignment_s": host_s, "wait_for_copy_s": copy_s})
+
+
+# ------------------------------------------------------------------------------------------------------------------ the descriptor network
+from .matching_encoder import PointNet2PTMSGDynamic                          # noqa: E402  (the matcher's modules are re-exported here)
+from .matching_transformer import CrossAttentionLayer, PointTransformerLayer  # noqa: E402
+
+DESCRIPTOR_PREFIXES = ("encoder.", "tf_self1.", "tf_cross1.")
+
+
+class DescriptorNetwork(nn.Module):
+    """encoder, tf_self1 and tf_cross1 of JointSegmentationAlignmentModel (joint_seg_align_model.py:38-50, 146-162) with the reference's
+    parameter names: the points of several puzzles -> flat per-point descriptors [sum N, 128] in the layout MatchingHead.forward
+    takes.  Everything between the upload of the points and the descriptors runs on the device; the piece lengths are host data."""
+
+    def __init__(self, gemm_mode: str = "f32"):
+        super().__init__()
+        self.gemm_mode = gemm_mode
+        self.encoder = PointNet2PTMSGDynamic(3, PC_FEAT_DIM, gemm_mode=gemm_mode)
+        self.tf_self1 = PointTransformerLayer(PC_FEAT_DIM, PC_FEAT_DIM, n_heads=8, nsampmle=16, gemm_mode=gemm_mode)
+        self.tf_cross1 = CrossAttentionLayer(PC_FEAT_DIM, 8, gemm_mode=gemm_mode)
+        super().train(False)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise NotImplementedError("DescriptorNetwork runs in eval mode only: matcher training is not built")
+        return super().train(False)
+
+    @classmethod
+    def from_checkpoint(cls, path: str, **kw) -> "DescriptorNetwork":
+        """the `encoder.*`, `tf_self1.*` and `tf_cross1.*` entries of a Jigsaw checkpoint (strict); the rest is ignored"""
+        sd = load_checkpoint_state_dict(path)
+        net = cls(**kw)
+        net.load_state_dict({k: v for k, v in sd.items() if k.startswith(DESCRIPTOR_PREFIXES)}, strict=True)
+        return net
+
+    @torch.no_grad()
+    def forward(self, part_pcs, n_pcs, part_valids, start=None, seed: Optional[int] = None) -> torch.Tensor:
+        """part_pcs: float32 [B, N, 3], a list of [N_b, 3] or flat [sum N, 3] on the GPU; n_pcs int [B, P]; part_valids [B, P];
+        start / seed: the encoder's sampling starts ([number of non-empty pieces, 4]) or the seed they are drawn from"""
+        first = part_pcs[0] if isinstance(part_pcs, (list, tuple)) else part_pcs
+        _gpu(first, torch.float32, "part_pcs")
+        layout = make_layout(n_pcs, first.device)
+        pts = _flatten(part_pcs, layout, 3, "part_pcs")
+        B, P = layout.n_pcs.shape
+        pv = np.asarray(part_valids.detach().cpu().numpy() if torch.is_tensor(part_valids) else part_valids)
+        n_valid = pv.reshape(B, P).sum(1).astype(np.int64)
+        for b in range(B):
+            if layout.n_pcs[b, n_valid[b]:].any() or (layout.n_pcs[b, :n_valid[b]] < 1).any():
+                raise ValueError(f"puzzle {b}: its {n_valid[b]} valid pieces must be the first slots and hold at least one point each")
+        lengths = layout.n_pcs.reshape(-1)
+        lengths = lengths[lengths > 0]                    # get_batch_length_from_part_points: the valid pieces of all puzzles in order
+        feats = self.encoder(pts, lengths, start=start, seed=seed)
+        feats = self.tf_self1(pts, feats, lengths)
+        return self.tf_cross1(feats, layout.puz_points)
