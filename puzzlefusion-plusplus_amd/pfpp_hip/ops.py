@@ -58,6 +58,15 @@ def _chk(t: torch.Tensor, dtype: torch.dtype, name: str) -> torch.Tensor:
     return t
 
 
+def _chk_rows(t: torch.Tensor, dtype: torch.dtype, name: str) -> torch.Tensor:
+    """_chk for a 2-d operand that is handed over with its row stride: contiguous, or a column slice of a wider contiguous tensor
+    (one row is enough for dtype, device and the unit column stride; the alignment of the pointer and of stride(0) is left to the
+    PFPP_REQUIRE lines of the C entry point the stride goes to)"""
+    if isinstance(t, torch.Tensor) and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return _chk(t[:1], dtype, name)
+    return _chk(t, dtype, name)
+
+
 def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -322,9 +331,10 @@ def gemm(A: torch.Tensor, W, *, M: int, N: int, K: int, lda: int, ldw: Optional[
          batch: int = 1, zdiv: int = 1, sA=(0, 0), sW=(0, 0), sC=(0, 0), sV=(0, 0), alpha: float = 1.0,
          a_off: int = 0, w_off: int = 0, c_off: int = 0, mode: Optional[str] = None,
          a_affine=None, stats: Optional[torch.Tensor] = None, c_min: Optional[torch.Tensor] = None,
-         gather=None) -> torch.Tensor:
+         gather=None, r_off: Optional[int] = None) -> torch.Tensor:
     """Raw pfpp_gemm call.  A/W/out are base tensors; *_off are element offsets into them
-    (used to address q/k/v slices of a packed projection without copies).  W is an fp32 tensor or a
+    (used to address q/k/v slices of a packed projection without copies; the residual is read at c_off unless r_off is given).
+    W is an fp32 tensor or a
     packing.PW (fp32 + pre-split fp16 planes); `mode` overrides ops.GEMM_MODE for this call."""
     from .packing import PW
 
@@ -396,7 +406,7 @@ def gemm(A: torch.Tensor, W, *, M: int, N: int, K: int, lda: int, ldw: Optional[
     args.bias = 0 if bias is None else bias.data_ptr()
     args.scale = 0 if scale is None else scale.data_ptr()
     args.shift = 0 if shift is None else shift.data_ptr()
-    args.residual = 0 if residual is None else residual.data_ptr() + c_off * es
+    args.residual = 0 if residual is None else residual.data_ptr() + (c_off if r_off is None else r_off) * es
     args.M, args.N, args.K = M, N, K
     args.lda, args.ldw, args.ldc, args.ldr = lda, ldw, ldc, ldr
     args.w_kmajor = int(w_kmajor)
@@ -872,7 +882,7 @@ def gemm_small(a, w, *, bias: Optional[torch.Tensor] = None, residual: Optional[
     pw = PwC(w.f32.data_ptr(), w.hi.data_ptr(), w.lo.data_ptr(), w.scale, w.hi.shape[-1], fh.data_ptr(), fl.data_ptr())
     for t_, nm in ((bias, "bias"), (residual, "residual"), (out, "out")):
         if t_ is not None:
-            _chk(t_, torch.float32, nm)
+            (_chk if nm == "bias" else _chk_rows)(t_, torch.float32, nm)
     if out is None:
         out = torch.empty((M, w.N), dtype=torch.float32, device=a.hi.device)
     ap = PlanesC(a.hi.data_ptr(), a.lo.data_ptr(), 1.0)
@@ -910,7 +920,7 @@ def gemm_wd(a, w, *, bias: Optional[torch.Tensor] = None, residual: Optional[tor
     pw = PwC(w.f32.data_ptr(), w.hi.data_ptr(), w.lo.data_ptr(), w.scale, w.hi.shape[-1], fh.data_ptr(), fl.data_ptr())
     for t_, nm in ((bias, "bias"), (residual, "residual"), (out, "out")):
         if t_ is not None:
-            _chk(t_, torch.float32, nm)
+            (_chk if nm == "bias" else _chk_rows)(t_, torch.float32, nm)
     if out is None:
         out = torch.empty((M, w.N), dtype=torch.float32, device=a.hi.device)
     ap = PlanesC(a.hi.data_ptr(), a.lo.data_ptr(), 1.0)

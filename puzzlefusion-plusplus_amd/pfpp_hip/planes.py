@@ -99,8 +99,11 @@ def gemm(A: Planes, W: Planes, out: torch.Tensor, *, M: int, N: int, K: int, a_k
          bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, act: str = "none",
          accumulate: bool = False, splits: int = 0, variant: int = 0, alpha: Optional[float] = None, use_ws: bool = True,
          single_pass: bool = False, colsum: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
-         defer: Optional["SlabJob"] = None) -> torch.Tensor:
+         defer: Optional["SlabJob"] = None, lda: Optional[int] = None, ldw: Optional[int] = None, ldc: Optional[int] = None,
+         ldr: Optional[int] = None, a_off: int = 0, w_off: int = 0, c_off: int = 0, r_off: int = 0) -> torch.Tensor:
     """pfpp_gemm_planes: out [M, N] = act(alpha * A.W + bias) + residual, or += with accumulate.
+    ld* / *_off: leading dimensions and element offsets into A / W / out / residual taken as base tensors (defaults: the tensors' own
+    last dimension, no offset).
        forward  : A [M, K],              W [N, K]
        dX       : A = dY [M, K],         W [K, N] (w_kmajor)
        dW       : A = dY [K, M] (a_kmajor), W = X [K, N] (w_kmajor)
@@ -108,14 +111,16 @@ def gemm(A: Planes, W: Planes, out: torch.Tensor, *, M: int, N: int, K: int, a_k
     gradient), computed inside the same kernel."""
     _chk(out, _f32, "out")
     a = GemmPlanesArgs()
-    a.a_hi, a.a_lo, a.w_hi, a.w_lo = A.hi.data_ptr(), A.lo.data_ptr(), W.hi.data_ptr(), W.lo.data_ptr()
-    a.C = out.data_ptr()
+    a.a_hi, a.a_lo = A.hi.data_ptr() + 2 * a_off, A.lo.data_ptr() + 2 * a_off
+    a.w_hi, a.w_lo = W.hi.data_ptr() + 2 * w_off, W.lo.data_ptr() + 2 * w_off
+    a.C = out.data_ptr() + 4 * c_off
     a.bias = 0 if bias is None else bias.data_ptr()
-    a.residual = 0 if residual is None else residual.data_ptr()
+    a.residual = 0 if residual is None else residual.data_ptr() + 4 * r_off
     a.M, a.N, a.K = M, N, K
-    a.lda, a.ldw = A.hi.shape[-1], W.hi.shape[-1]
-    a.ldc = out.shape[-1]
-    a.ldr = 0 if residual is None else residual.shape[-1]
+    a.lda = A.hi.shape[-1] if lda is None else lda
+    a.ldw = W.hi.shape[-1] if ldw is None else ldw
+    a.ldc = out.shape[-1] if ldc is None else ldc
+    a.ldr = 0 if residual is None else (residual.shape[-1] if ldr is None else ldr)
     a.a_kmajor, a.w_kmajor = int(a_kmajor), int(w_kmajor)
     a.act = ACT[act]
     a.accumulate = int(accumulate)
@@ -191,7 +196,7 @@ def gemm_wd(A: "Planes", W: "Planes", out: torch.Tensor, *, M: int, N: int, K: i
     from . import ops
     from ._lib import PlanesC, PwC, ReblockJob
 
-    _chk(out, _f32, "out")
+    ops._chk_rows(out, _f32, "out")                             # (out / residual may be column slices of wider tensors: their row strides go along)
     lib = _lib.load()
     rows, cols = (K, N) if transposed else (N, K)               # W as stored
     if frag is not None:                                        # blocked beforehand (reblock_many)
@@ -212,8 +217,8 @@ def gemm_wd(A: "Planes", W: "Planes", out: torch.Tensor, *, M: int, N: int, K: i
     if ev:
         ev[1].record(); ev[2].record()
     check(lib.pfpp_gemm_wd(C.byref(ap), A.hi.shape[-1], C.byref(pw), None if bias is None else bias.data_ptr(),
-                           None if residual is None else residual.data_ptr(), 0 if residual is None else residual.shape[-1],
-                           out.data_ptr(), out.shape[-1], M, N, K, _stream()), "pfpp_gemm_wd")
+                           None if residual is None else residual.data_ptr(), 0 if residual is None else residual.stride(0),
+                           out.data_ptr(), out.stride(0), M, N, K, _stream()), "pfpp_gemm_wd")
     if ev:
         ev[3].record()
         big = N % 256 == 0 and ((M + 127) // 128) * (N // 256) >= 240

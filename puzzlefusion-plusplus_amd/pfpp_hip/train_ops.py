@@ -103,7 +103,7 @@ def grad_weight_group(problems, *, g_scale: float = 1.0) -> None:
     arr = (GemmGradArgs * n)()
     flops = 0.0
     for a, (dY, X, dW) in zip(arr, problems):
-        _chk(dY, _f32, "dY"); _chk(X, _f32, "X"); _chk(dW, _f32, "dW")
+        ops._chk_rows(dY, _f32, "dY"); ops._chk_rows(X, _f32, "X"); ops._chk_rows(dW, _f32, "dW")
         M, N_out = dY.shape
         if X.shape[0] != M or dW.shape[0] != N_out or dW.shape[1] > X.shape[1]:
             raise ValueError("grad_weight_group: shape mismatch")
