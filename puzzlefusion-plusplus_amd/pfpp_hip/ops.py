@@ -794,17 +794,20 @@ def token_combine_list(shape_emb, x_emb, ref_emb, ref_u8, pe, frag_pos, L, slot=
 
 
 def layernorm_grouped(x: torch.Tensor, mod: torch.Tensor, group_batch: torch.Tensor, group_rows: int,
-                      eps: float = 1e-5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """AdaLN over a compacted token list: the batch (row of `mod`) of token r is group_batch[r // group_rows]"""
+                      eps: float = 1e-5, out: Optional[torch.Tensor] = None, ld_mod: Optional[int] = None) -> torch.Tensor:
+    """AdaLN over a compacted token list: the batch (row of `mod`) of token r is group_batch[r // group_rows];
+    ld_mod: row stride of `mod` when its rows are wider than 2C (default: mod.shape[-1])"""
     _chk(x, torch.float32, "x"); _chk(mod, torch.float32, "mod"); _chk(group_batch, torch.int32, "group_batch")
     rows, Cc = x.shape
+    if ld_mod is None:
+        ld_mod = mod.shape[-1]
     if isinstance(out, SplitAct):
-        check(_lib.load().pfpp_layernorm_grouped_split(_ptr(x), _ptr(out.hi), _ptr(out.lo), _ptr(mod), mod.shape[-1], _ptr(group_batch),
+        check(_lib.load().pfpp_layernorm_grouped_split(_ptr(x), _ptr(out.hi), _ptr(out.lo), _ptr(mod), ld_mod, _ptr(group_batch),
                                                        group_rows, rows, Cc, eps, _stream()), "pfpp_layernorm_grouped_split")
         return out
     if out is None:
         out = torch.empty_like(x)
-    check(_lib.load().pfpp_layernorm_grouped(_ptr(x), _ptr(out), _ptr(mod), mod.shape[-1], _ptr(group_batch), group_rows,
+    check(_lib.load().pfpp_layernorm_grouped(_ptr(x), _ptr(out), _ptr(mod), ld_mod, _ptr(group_batch), group_rows,
                                              rows, Cc, eps, _stream()), "pfpp_layernorm_grouped")
     return out
 
@@ -822,17 +825,20 @@ def silu_embed(tables: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
 
 def layernorm(x: torch.Tensor, *, mod: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None,
               beta: Optional[torch.Tensor] = None, rows_per_batch: int = 1, eps: float = 1e-5,
-              out=None):
+              out=None, ld_mod: Optional[int] = None):
     """x [rows, C]; mod [B, 2C] (AdaLN scale|shift) or gamma/beta [C]; `out` may be a SplitAct (the
-    normalised rows are then written as split-f16 planes for the next GEMM)"""
+    normalised rows are then written as split-f16 planes for the next GEMM); ld_mod: row stride of `mod` when its
+    rows are wider than 2C (default: mod is exactly [B, 2C])"""
     _chk(x, torch.float32, "x")
     rows, Cc = x.shape
-    ld_mod = 0
     if mod is not None:
         _chk(mod, torch.float32, "mod")
-        ld_mod = mod.shape[-1]
-        if ld_mod != 2 * Cc:
-            raise ValueError("layernorm: mod must be [B, 2C]")
+        if ld_mod is None:
+            ld_mod = mod.shape[-1]
+            if ld_mod != 2 * Cc:
+                raise ValueError("layernorm: mod must be [B, 2C]")
+    else:
+        ld_mod = 0
     if gamma is not None:
         _chk(gamma, torch.float32, "gamma"); _chk(beta, torch.float32, "beta")
     if isinstance(out, SplitAct):
@@ -1035,10 +1041,11 @@ def softmax_rows(S: torch.Tensor, key_valid_u8: Optional[torch.Tensor], rows_per
     return S
 
 
-def mean_pool(x: torch.Tensor, n: int, L: int) -> torch.Tensor:
+def mean_pool(x: torch.Tensor, n: int, L: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(x, torch.float32, "x")
     Cc = x.shape[-1]
-    out = torch.empty((n, Cc), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((n, Cc), dtype=torch.float32, device=x.device)
     check(_lib.load().pfpp_mean_pool(_ptr(x), _ptr(out), n, L, Cc, _stream()), "pfpp_mean_pool")
     return out
 

@@ -63,11 +63,14 @@ def split(x: torch.Tensor, scale: float = 1.0, out: Optional[Planes] = None) -> 
     return out
 
 
-def colsum(p: Planes, out: torch.Tensor) -> torch.Tensor:
-    """out[c] += sum over rows of the tensor `p` stands for (bias gradient of a dY given as planes)"""
+def colsum(p: Planes, out: torch.Tensor, cols: Optional[int] = None) -> torch.Tensor:
+    """out[c] += sum over rows of the tensor `p` stands for (bias gradient of a dY given as planes); cols: the planes are
+    [rows, ld] and only their first `cols` columns count"""
     _chk(out, _f32, "out")
-    rows, cols = p.shape
-    check(_lib.load().pfpp_colsum_planes(_ptr(p.hi), _ptr(p.lo), _ptr(out), rows, cols, cols, 1.0 / p.scale, _stream()),
+    rows, ld = p.shape
+    if cols is None:
+        cols = ld
+    check(_lib.load().pfpp_colsum_planes(_ptr(p.hi), _ptr(p.lo), _ptr(out), rows, cols, ld, 1.0 / p.scale, _stream()),
           "pfpp_colsum_planes")
     return out
 

@@ -150,8 +150,11 @@ def dropout(x: torch.Tensor, p: float, seed: int, site: int, *, res: Optional[to
     return out
 
 
-def dropout_mask(n: int, p: float, seed: int, site: int, device) -> torch.Tensor:
-    keep = torch.empty((n,), dtype=torch.uint8, device=device)
+def dropout_mask(n: int, p: float, seed: int, site: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [n]: the keep mask of that site; out: where it goes (default: a new tensor)"""
+    if out is not None:
+        _chk(out, torch.uint8, "out")
+    keep = torch.empty((n,), dtype=torch.uint8, device=device) if out is None else out
     check(_lib.load().pfpp_dropout_mask(_ptr(keep), n, p, seed, site, _stream()), "pfpp_dropout_mask")
     return keep
 
@@ -177,16 +180,18 @@ def geglu_bwd(z: torch.Tensor, du: torch.Tensor, p: float = 0.0, seed: int = 0, 
     return out
 
 
-def act(pre: torch.Tensor, kind: str) -> torch.Tensor:
+def act(pre: torch.Tensor, kind: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(pre, _f32, "pre")
-    out = torch.empty_like(pre)
+    if out is None:
+        out = torch.empty_like(pre)
     check(_lib.load().pfpp_act(_ptr(pre), _ptr(out), pre.numel(), ACT[kind], _stream()), "pfpp_act")
     return out
 
 
-def act_bwd(pre: torch.Tensor, dy: torch.Tensor, kind: str) -> torch.Tensor:
+def act_bwd(pre: torch.Tensor, dy: torch.Tensor, kind: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(pre, _f32, "pre"); _chk(dy, _f32, "dy")
-    out = torch.empty_like(pre)
+    if out is None:
+        out = torch.empty_like(pre)
     check(_lib.load().pfpp_act_bwd(_ptr(pre), _ptr(dy), _ptr(out), pre.numel(), ACT[kind], _stream()), "pfpp_act_bwd")
     return out
 
@@ -195,9 +200,10 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, *, mod: O
                   gamma: Optional[torch.Tensor] = None, group_batch: Optional[torch.Tensor] = None,
                   group_rows: int = 32, rows_per_batch: int = 1, dmult: Optional[torch.Tensor] = None,
                   dadd: Optional[torch.Tensor] = None, ld_d: int = 0, eps: float = 1e-5,
-                  drop: Optional[tuple] = None) -> torch.Tensor:
+                  drop: Optional[tuple] = None, drop_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dx += LayerNorm backward; dmult/dadd (+)= the (scale, shift) / (gamma, beta) gradients (see pfpp.h).
-    drop = (p, seed, site): also returns dropout(dx) of that site as a new tensor (pfpp_layernorm_bwd_dropout) instead of dx"""
+    drop = (p, seed, site): also returns dropout(dx) of that site (pfpp_layernorm_bwd_dropout) instead of dx, as a new tensor
+    or in `drop_out`"""
     _chk(x, _f32, "x"); _chk(dy, _f32, "dy"); _chk(dx, _f32, "dx")
     rows, Cc = x.shape
     ld_mod = 0
@@ -210,7 +216,9 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, *, mod: O
             raise ValueError("layernorm_bwd: group_batch too short")
     if drop is not None:
         p, seed, site = drop
-        out = torch.empty_like(dx)
+        if drop_out is not None:
+            _chk(drop_out, _f32, "drop_out")
+        out = torch.empty_like(dx) if drop_out is None else drop_out
         check(_lib.load().pfpp_layernorm_bwd_dropout(_ptr(x), _ptr(dy), _ptr(mod), ld_mod, _ptr(gamma), _ptr(group_batch), group_rows,
                                                      rows_per_batch, _ptr(dx), _ptr(dmult), _ptr(dadd), ld_d, rows, Cc, eps, _ptr(out),
                                                      p, seed, site, _stream()), "pfpp_layernorm_bwd_dropout")
@@ -224,24 +232,28 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, *, mod: O
 def dropout_layernorm(y: torch.Tensor, res: Optional[torch.Tensor], p: float, seed: int, site: int, *,
                       mod: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None,
                       beta: Optional[torch.Tensor] = None, group_batch: Optional[torch.Tensor] = None, group_rows: int = 1,
-                      rows_per_batch: int = 1, eps: float = 1e-5):
+                      rows_per_batch: int = 1, eps: float = 1e-5, ld_mod: Optional[int] = None,
+                      n_out: Optional[torch.Tensor] = None):
     """-> (h, n): h = (res or 0) + dropout(y) written over y, n = LayerNorm(h) (AdaLN `mod` [B, 2C] or gamma/beta) — one launch
-    for pfpp_dropout + pfpp_layernorm (pfpp_dropout_layernorm)"""
+    for pfpp_dropout + pfpp_layernorm (pfpp_dropout_layernorm).  ld_mod: row stride of a `mod` whose rows are wider than 2C;
+    n_out: where n goes (default: a new tensor)"""
     _chk(y, _f32, "y")
     rows, Cc = y.shape
-    ld_mod = 0
     if res is not None:
         _chk(res, _f32, "res")
     if mod is not None:
         _chk(mod, _f32, "mod")
-        ld_mod = mod.stride(0)
-        if mod.shape[-1] != 2 * Cc:
-            raise ValueError("dropout_layernorm: mod must be [B, 2C]")
+        if ld_mod is None:                     # (given: the row stride of a `mod` whose rows are wider than 2C)
+            ld_mod = mod.stride(0)
+            if mod.shape[-1] != 2 * Cc:
+                raise ValueError("dropout_layernorm: mod must be [B, 2C]")
+    else:
+        ld_mod = 0
     if group_batch is not None:
         _chk(group_batch, torch.int32, "group_batch")
         if group_batch.numel() * group_rows < rows:
             raise ValueError("dropout_layernorm: group_batch too short")
-    n = torch.empty_like(y)
+    n = torch.empty_like(y) if n_out is None else n_out
     check(_lib.load().pfpp_dropout_layernorm(_ptr(y), _ptr(res), _ptr(y), _ptr(n), _ptr(mod), ld_mod, _ptr(gamma), _ptr(beta),
                                              _ptr(group_batch), group_rows, rows_per_batch, rows, Cc, eps, p, seed, site, _stream()),
           "pfpp_dropout_layernorm")
@@ -442,27 +454,38 @@ def ada_linear_bwd(dmods: torch.Tensor, se: torch.Tensor, w: torch.Tensor, g_w: 
 
 
 def mse_loss_masked(pred: torch.Tensor, target: torch.Tensor, valid: torch.Tensor, ref_u8: torch.Tensor, grad_out: float = 1.0,
-                    amax: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                    amax: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None,
+                    dpred_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """mse_loss over the rows with valid != 0 and ref == 0, the selection never materialised (pfpp_mse_loss_masked); amax [1]
-    receives max |dpred|"""
+    receives max |dpred|; loss_out [1] / dpred_out [n, width]: where the results go (default: new tensors)"""
     _chk(pred, _f32, "pred"); _chk(target, _f32, "target"); _chk(valid, _f32, "valid"); _chk(ref_u8, torch.uint8, "ref")
     n, width = pred.shape
     if valid.numel() != n or ref_u8.numel() != n:
         raise ValueError("mse_loss_masked: valid / ref must have one entry per row")
-    loss = torch.empty((1,), dtype=_f32, device=pred.device)
-    dpred = torch.empty_like(pred)
+    if loss_out is not None:
+        _chk(loss_out, _f32, "loss_out")
+    if dpred_out is not None:
+        _chk(dpred_out, _f32, "dpred_out")
+    loss = torch.empty((1,), dtype=_f32, device=pred.device) if loss_out is None else loss_out
+    dpred = torch.empty_like(pred) if dpred_out is None else dpred_out
     check(_lib.load().pfpp_mse_loss_masked(_ptr(pred), _ptr(target), _ptr(valid), _ptr(ref_u8), _ptr(loss), _ptr(dpred), _ptr(amax), n,
                                            width, grad_out, _stream()), "pfpp_mse_loss_masked")
     return loss, dpred
 
 
 def mse_loss(pred: torch.Tensor, target: torch.Tensor, sel_u8: torch.Tensor, grad_out: float = 1.0,
-             need_grad: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """-> (loss [1], dpred) over the rows with sel != 0 (Denoiser._loss)"""
+             need_grad: bool = True, loss_out: Optional[torch.Tensor] = None,
+             dpred_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """-> (loss [1], dpred) over the rows with sel != 0 (Denoiser._loss); loss_out [1] / dpred_out [n, width]: where the
+    results go (default: new tensors)"""
     _chk(pred, _f32, "pred"); _chk(target, _f32, "target"); _chk(sel_u8, torch.uint8, "sel")
     n, width = pred.shape
-    loss = torch.empty((1,), dtype=_f32, device=pred.device)
-    dpred = torch.empty_like(pred) if need_grad else None
+    if loss_out is not None:
+        _chk(loss_out, _f32, "loss_out")
+    if dpred_out is not None:
+        _chk(dpred_out, _f32, "dpred_out")
+    loss = torch.empty((1,), dtype=_f32, device=pred.device) if loss_out is None else loss_out
+    dpred = (torch.empty_like(pred) if dpred_out is None else dpred_out) if need_grad else None
     check(_lib.load().pfpp_mse_loss(_ptr(pred), _ptr(target), _ptr(sel_u8), _ptr(loss), _ptr(dpred), n, width, grad_out,
                                     _stream()), "pfpp_mse_loss")
     return loss, dpred
@@ -525,13 +548,21 @@ def adamw_rows_active(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torc
 
 
 def bn_stats(x: torch.Tensor, running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
-             momentum: float = 0.1) -> Tuple[torch.Tensor, torch.Tensor]:
+             momentum: float = 0.1, cols: Optional[int] = None,
+             out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """per-column batch mean / biased variance of x [rows, C]; updates the running statistics in place like
-    nn.BatchNorm2d in train mode (utils/pn2_utils.py:211-214)"""
+    nn.BatchNorm2d in train mode (utils/pn2_utils.py:211-214).  cols: x is [rows, ld] and only its first `cols` columns count;
+    out: (mean [C], var [C]) to write into (default: new tensors)"""
     _chk(x, _f32, "x")
     rows, Cc = x.shape
-    mean = torch.empty((Cc,), dtype=_f32, device=x.device)
-    var = torch.empty((Cc,), dtype=_f32, device=x.device)
+    if cols is not None:
+        Cc = cols
+    if out is not None:
+        mean, var = out
+        _chk(mean, _f32, "mean"); _chk(var, _f32, "var")
+    else:
+        mean = torch.empty((Cc,), dtype=_f32, device=x.device)
+        var = torch.empty((Cc,), dtype=_f32, device=x.device)
     lib = _lib.load()
     ws = torch.empty((int(lib.pfpp_bn_stats_workspace(rows, Cc)),), dtype=torch.uint8, device=x.device)
     if running_mean is not None:
@@ -542,15 +573,20 @@ def bn_stats(x: torch.Tensor, running_mean: Optional[torch.Tensor] = None, runni
 
 
 def bn_apply(x: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
-             eps: float = 1e-5, pool: int = 0) -> torch.Tensor:
-    """relu(batch-norm(x)) with the given statistics, optional max over groups of `pool` rows"""
+             eps: float = 1e-5, pool: int = 0, cols: Optional[int] = None, out: Optional[torch.Tensor] = None,
+             ldy: Optional[int] = None) -> torch.Tensor:
+    """relu(batch-norm(x)) with the given statistics, optional max over groups of `pool` rows.  cols: x is [rows, ld] and only
+    its first `cols` columns count; out / ldy: the result goes into `out`, whose rows are ldy floats apart"""
     _chk(x, _f32, "x")
     for t_, nm in ((mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta")):
         _chk(t_, _f32, nm)
     rows, Cc = x.shape
-    out = torch.empty((rows // pool if pool else rows, Cc), dtype=_f32, device=x.device)
+    if cols is not None:
+        Cc = cols
+    if out is None:
+        out = torch.empty((rows // pool if pool else rows, Cc), dtype=_f32, device=x.device)
     check(_lib.load().pfpp_bn_apply(_ptr(x), rows, Cc, x.stride(0), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), eps,
-                                    _ptr(out), Cc, pool, _stream()), "pfpp_bn_apply")
+                                    _ptr(out), Cc if ldy is None else ldy, pool, _stream()), "pfpp_bn_apply")
     return out
 
 
@@ -563,26 +599,37 @@ def bn_stats_buffer(C: int, device) -> torch.Tensor:
 
 def bn_finalize(stats: torch.Tensor, rows: int, gamma: torch.Tensor, beta: torch.Tensor,
                 running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
-                momentum: float = 0.1, eps: float = 1e-5, want_stats: bool = False):
+                momentum: float = 0.1, eps: float = 1e-5, want_stats: bool = False, out: Optional[tuple] = None):
     """stats accumulated by a GEMM epilogue -> (a_mul, a_add) for the consumer [+ (mean, var)]; updates the running
-    buffers like nn.BatchNorm2d in train mode and clears `stats`"""
+    buffers like nn.BatchNorm2d in train mode and clears `stats`.  out: (a_mul, a_add[, mean, var]), each [C], to write into
+    (default: new tensors)"""
     _chk(stats, torch.float64, "stats"); _chk(gamma, _f32, "gamma"); _chk(beta, _f32, "beta")
     Cc = stats.shape[2]
-    a_mul = torch.empty((Cc,), dtype=_f32, device=stats.device)
-    a_add = torch.empty((Cc,), dtype=_f32, device=stats.device)
-    mean = torch.empty((Cc,), dtype=_f32, device=stats.device) if want_stats else None
-    var = torch.empty((Cc,), dtype=_f32, device=stats.device) if want_stats else None
+    if out is not None:
+        if len(out) != (4 if want_stats else 2):
+            raise ValueError("bn_finalize: out must be (a_mul, a_add) or, with want_stats, (a_mul, a_add, mean, var)")
+        for t_ in out:
+            _chk(t_, _f32, "out")
+        a_mul, a_add = out[:2]
+        mean, var = out[2:] if want_stats else (None, None)
+    else:
+        a_mul = torch.empty((Cc,), dtype=_f32, device=stats.device)
+        a_add = torch.empty((Cc,), dtype=_f32, device=stats.device)
+        mean = torch.empty((Cc,), dtype=_f32, device=stats.device) if want_stats else None
+        var = torch.empty((Cc,), dtype=_f32, device=stats.device) if want_stats else None
     check(_lib.load().pfpp_bn_finalize(_ptr(stats), stats.shape[0], rows, Cc, _ptr(gamma), _ptr(beta), eps, momentum,
                                        _ptr(running_mean), _ptr(running_var), _ptr(mean), _ptr(var), _ptr(a_mul), _ptr(a_add),
                                        _stream()), "pfpp_bn_finalize")
     return (a_mul, a_add, mean, var) if want_stats else (a_mul, a_add)
 
 
-def bn_minmax_apply(mx: torch.Tensor, mn: torch.Tensor, a_mul: torch.Tensor, a_add: torch.Tensor) -> torch.Tensor:
+def bn_minmax_apply(mx: torch.Tensor, mn: torch.Tensor, a_mul: torch.Tensor, a_add: torch.Tensor,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """max over a pool group of relu(a*x + b), from the group's max and min of x"""
     _chk(mx, _f32, "mx"); _chk(mn, _f32, "mn"); _chk(a_mul, _f32, "a_mul"); _chk(a_add, _f32, "a_add")
     rows, Cc = mx.shape
-    out = torch.empty_like(mx)
+    if out is None:
+        out = torch.empty_like(mx)
     check(_lib.load().pfpp_bn_minmax_apply(_ptr(mx), _ptr(mn), _ptr(a_mul), _ptr(a_add), _ptr(out), rows, Cc, _stream()),
           "pfpp_bn_minmax_apply")
     return out
@@ -591,24 +638,27 @@ def bn_minmax_apply(mx: torch.Tensor, mn: torch.Tensor, a_mul: torch.Tensor, a_a
 # ------------------------------------------------------------------------------------------------------------------
 # plane-producing forms (include/pfpp.h): the result goes out as split-f16 planes for the plane GEMM (pfpp_hip.planes)
 # ------------------------------------------------------------------------------------------------------------------
-def geglu_planes(z: torch.Tensor, p: float, seed: int, site: int):
-    """-> Planes of u = value * gelu(gate) (+ dropout) [rows, inner]; no fp32 copy"""
+def geglu_planes(z: torch.Tensor, p: float, seed: int, site: int, out=None):
+    """-> Planes of u = value * gelu(gate) (+ dropout) [rows, inner]; no fp32 copy.  out: the Planes (scale 1) to write into"""
     from .planes import Planes, _pl
 
     _chk(z, _f32, "z")
     rows, two_inner = z.shape
-    out = Planes.empty(rows, two_inner // 2, z.device)
+    if out is None:
+        out = Planes.empty(rows, two_inner // 2, z.device)
     check(_lib.load().pfpp_geglu_p(_ptr(z), None, rows, two_inner // 2, p, seed, site, _pl(out), _stream()), "pfpp_geglu_p")
     return out
 
 
-def geglu_bwd_planes(z: torch.Tensor, du: torch.Tensor, p: float, seed: int, site: int, scale: float):
-    """-> Planes of scale * dz [rows, 2 inner]; no fp32 copy"""
+def geglu_bwd_planes(z: torch.Tensor, du: torch.Tensor, p: float, seed: int, site: int, scale: float, out=None):
+    """-> Planes of scale * dz [rows, 2 inner]; no fp32 copy.  out: the Planes to write into (its scale becomes `scale`)"""
     from .planes import Planes, _pl
 
     _chk(z, _f32, "z"); _chk(du, _f32, "du")
     rows, two_inner = z.shape
-    out = Planes.empty(rows, two_inner, z.device, scale)
+    if out is None:
+        out = Planes.empty(rows, two_inner, z.device, scale)
+    out.scale = float(scale)
     check(_lib.load().pfpp_geglu_bwd_p(_ptr(z), _ptr(du), None, rows, two_inner // 2, p, seed, site, _pl(out), _stream()),
           "pfpp_geglu_bwd_p")
     return out
@@ -617,25 +667,28 @@ def geglu_bwd_planes(z: torch.Tensor, du: torch.Tensor, p: float, seed: int, sit
 def dropout_layernorm_planes(y: torch.Tensor, res: Optional[torch.Tensor], p: float, seed: int, site: int, *,
                              mod: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None,
                              beta: Optional[torch.Tensor] = None, group_batch: Optional[torch.Tensor] = None, group_rows: int = 1,
-                             rows_per_batch: int = 1, eps: float = 1e-5):
-    """dropout_layernorm with the normalised rows as Planes: -> (h written over y, Planes n)"""
+                             rows_per_batch: int = 1, eps: float = 1e-5, ld_mod: Optional[int] = None, n_out=None):
+    """dropout_layernorm with the normalised rows as Planes: -> (h written over y, Planes n).  n_out: the Planes (scale 1) that
+    receive n (default: new ones)"""
     from .planes import Planes, _pl
 
     _chk(y, _f32, "y")
     rows, Cc = y.shape
-    ld_mod = 0
     if res is not None:
         _chk(res, _f32, "res")
     if mod is not None:
         _chk(mod, _f32, "mod")
-        ld_mod = mod.stride(0)
-        if mod.shape[-1] != 2 * Cc:
-            raise ValueError("dropout_layernorm: mod must be [B, 2C]")
+        if ld_mod is None:                     # (given: the row stride of a `mod` whose rows are wider than 2C)
+            ld_mod = mod.stride(0)
+            if mod.shape[-1] != 2 * Cc:
+                raise ValueError("dropout_layernorm: mod must be [B, 2C]")
+    else:
+        ld_mod = 0
     if group_batch is not None:
         _chk(group_batch, torch.int32, "group_batch")
         if group_batch.numel() * group_rows < rows:
             raise ValueError("dropout_layernorm: group_batch too short")
-    n = Planes.empty(rows, Cc, y.device)
+    n = Planes.empty(rows, Cc, y.device) if n_out is None else n_out
     check(_lib.load().pfpp_dropout_layernorm_p(_ptr(y), _ptr(res), _ptr(y), None, _ptr(mod), ld_mod, _ptr(gamma), _ptr(beta),
                                                _ptr(group_batch), group_rows, rows_per_batch, rows, Cc, eps, p, seed, site,
                                                _pl(n), _stream()), "pfpp_dropout_layernorm_p")
@@ -647,9 +700,11 @@ def layernorm_bwd_planes(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, sc
                          group_rows: int = 32, rows_per_batch: int = 1, dmult: Optional[torch.Tensor] = None,
                          dadd: Optional[torch.Tensor] = None, ld_d: int = 0, eps: float = 1e-5,
                          drop: Optional[tuple] = None, want_ret: bool = True, want_dx: bool = False,
-                         ret_fp32: bool = False):
+                         ret_fp32: bool = False, ret_out=None, dx_out=None, drop_out: Optional[torch.Tensor] = None):
     """layernorm_bwd (dx += ..., in place) that also emits Planes (scale * value) of what the backward chain continues with
-    (`ret`: dropout(dx) for drop = (p, seed, site), else dx) and / or of the updated dx.  -> (ret_planes, dx_planes, ret_fp32_tensor)"""
+    (`ret`: dropout(dx) for drop = (p, seed, site), else dx) and / or of the updated dx.  -> (ret_planes, dx_planes, ret_fp32_tensor).
+    ret_out / dx_out: the Planes to write into (their scale becomes `scale`), drop_out: the fp32 tensor that receives
+    dropout(dx) (defaults: new ones)"""
     from .planes import Planes, _pl
 
     _chk(x, _f32, "x"); _chk(dy, _f32, "dy"); _chk(dx, _f32, "dx")
@@ -663,9 +718,14 @@ def layernorm_bwd_planes(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, sc
         if group_batch.numel() * group_rows < rows:
             raise ValueError("layernorm_bwd: group_batch too short")
     p, seed, site = drop if drop is not None else (0.0, 0, 0)
-    ret = Planes.empty(rows, Cc, x.device, scale) if want_ret else None
-    dxp = Planes.empty(rows, Cc, x.device, scale) if want_dx else None
-    out32 = torch.empty_like(dx) if (ret_fp32 and drop is not None) else None
+    ret = (Planes.empty(rows, Cc, x.device, scale) if ret_out is None else ret_out) if want_ret else None
+    dxp = (Planes.empty(rows, Cc, x.device, scale) if dx_out is None else dx_out) if want_dx else None
+    for pl_ in (ret, dxp):
+        if pl_ is not None:
+            pl_.scale = float(scale)
+    if drop_out is not None:
+        _chk(drop_out, _f32, "drop_out")
+    out32 = (torch.empty_like(dx) if drop_out is None else drop_out) if (ret_fp32 and drop is not None) else None
     check(_lib.load().pfpp_layernorm_bwd_p(_ptr(x), _ptr(dy), _ptr(mod), ld_mod, _ptr(gamma), _ptr(group_batch), group_rows,
                                            rows_per_batch, _ptr(dx), _ptr(dmult), _ptr(dadd), ld_d, rows, Cc, eps, _ptr(out32),
                                            p, seed, site, int(drop is not None), _pl(ret), _pl(dxp), _stream()),

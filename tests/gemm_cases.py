@@ -1073,15 +1073,19 @@ def run(c: Case, dev):
 def report_main() -> int:
     root = Path(__file__).resolve().parents[1]
     sys.path[:0] = [str(root), str(root / "puzzlefusion-plusplus_amd")]
+    from pfpp_hip._lib import PfppError
     dev = torch.device("cuda:0")
     bad = 0
     for name, c in CASES.items():
         try:
             rep, flags = run(c, dev)
-        except Exception as e:                                   # a rejected call is a line of the record too
+        except (ValueError, TypeError, PfppError) as e:          # a call the wrapper or the entry point rejects is a line of the record too
             print(f"gemm_edges {name:<32} ERROR {type(e).__name__}: {str(e)[:200]}", flush=True)
             bad += 1
             continue
+        except Exception as e:                                   # anything else (a HIP error): nothing more is launched
+            print(f"gemm_edges {name:<32} STOPPED {type(e).__name__}: {str(e)[:200]}", flush=True)
+            return 2
         print(describe(rep), flush=True)
         if flags.get("same_bits") is not None:
             print(f"gemm_edges {name:<32} same bits as the other entry point: {flags['same_bits']}", flush=True)
