@@ -1290,6 +1290,51 @@ int pfpp_attn_rows16(const float* qkv, float* out, const int32_t* seq_off, const
 int pfpp_layernorm128(const float* x, const float* gamma, const float* beta, float* out, int64_t rows, int64_t C, float eps,
                       pfpp_stream_t stream);
 
+/* ---- matcher head, training behind part_feats (Jigsaw_matching/model/jigsaw/joint_seg_align_model.py in .train(); csrc/matching_train.hip)
+ * Train-mode BatchNorm + ReLU, the linear layers, the affinity products and Adam go through pfpp_bn_stats / pfpp_bn_apply /
+ * pfpp_bn_relu_bwd, pfpp_gemm / pfpp_gemm_grad and pfpp_adamw; these entries are the rest of the step.
+ * pfpp_sinkhorn_train_fwd (utils/linear_solvers.py:188-207 unmasked, as called at joint_seg_align_model.py:266-268 in training, and
+ * utils/loss.py:26-56 for one puzzle): s [n, n] (row stride ld); L = s / tau in fp32; fp64 potentials from 0; step k even: u_i +=
+ * LSE_j((L_ij - u_i) - v_j), odd: the same for v_j over i; the vector step k wrote is kept in pots [max_iter, n] (fp64).  ds_mat [n, n]
+ * = exp((L - u) - v); loss [1] (fp64) = sum_ij BCE(ds_mat_ij, [j == tgt_i]) with both logs clamped at -100, summed in fp64 in a fixed
+ * order; tgt int32 [n], -1 = a row without a target (no dense gt_perm is built); row_loss (optional, fp64 [n]) receives the rows' shares.
+ * pfpp_sinkhorn_train_bwd (autograd of those lines): ds [n, n] (row stride ldg) = dLoss / ds, g = the upstream scale (w_mat_loss /
+ * sum_b n_b).  With G = dLoss / d log P: G_T = (P - y) P / max(P (1 - P), 1e-12) g (F.binary_cross_entropy's backward times P);
+ * for k = max_iter - 1 .. 0, P_k = exp((L - u_k) - v_k) from the stored potentials: even k: G -= P_k * rowsum(G), odd k: G -= P_k *
+ * colsum(G); ds = G_0 / tau.  G is ds itself, updated in place; the sums are fp64, the column sums through ordered partials; no
+ * float atomics, two runs agree bitwise; max_iter + 1 passes over the matrix, nothing of size [max_iter, n, n] is kept.
+ * workspace (both): pfpp_sinkhorn_train_workspace(n) bytes, -1 for n outside [0, 65535].
+ * pfpp_match_gt_targets (joint_seg_align_model.py:333-364): src int64 [R] = the global point index of every critical row (the rows
+ * of a puzzle contiguous, puz_row_off int64 [B + 1]), row_piece int32 [R] its piece; tgt int32 [R] = the puzzle-local column of the
+ * nearest critical point of ANOTHER piece of the puzzle, by max(-2 a.b + |a|^2 + |b|^2, 1e-12) in fp32, an exact tie to the lowest
+ * column; -1 where no other piece has a critical point (the reference's argmin lands in the own piece and `mask` zeroes it).
+ * max_rows = the largest puzzle's row count (<= 65535).
+ * pfpp_match_normalize_halves_bwd (:237-247): backward of pfpp_match_normalize_halves from the rows x before the normalisation:
+ * dx = dy / |x| - x (x . dy) / |x|^3 per half, dy / eps where |x| < eps = 1e-12.  dx may alias dy.  D = 512.
+ * pfpp_match_cls_bce (:298-323): loss [1] (fp64) = mean binary_cross_entropy_with_logits(logits, labels) (fp32 per element, fp64 sum, fixed
+ * order), dlogit (optional) = (sigmoid(logit) - y) g / N, counts int64 [4] = (tp, fp, tn, fn) of fp32 sigmoid(logit) > 0.5 against
+ * the label (what torchmetrics' binary accuracy / precision / recall / f1 are made of).  logits / dlogit are read / written with the
+ * strides ldl / ldd (a column of a wider matrix).  workspace: at least pfpp_match_cls_bce_workspace() bytes (workspace_bytes).
+ * pfpp_match_gather_raw (:110-116): out [R, 128] = feats[idx[r]] without BatchNorm or ReLU, a zero row where idx[r] is outside
+ * [0, N) (the zero padding of critical_feats up to the batch's largest N').  pfpp_match_scatter_raw: its transpose, out[idx[r]]
+ * = or += in[r] (accumulate); each point may occur at most once (plain stores, no atomics).                                      */
+int64_t pfpp_sinkhorn_train_workspace(int64_t n);
+int pfpp_sinkhorn_train_fwd(const float* s, int64_t ld, int64_t n, float tau, int64_t max_iter, const int32_t* tgt, double* pots,
+                            float* ds_mat, double* loss, double* row_loss, void* workspace, int64_t workspace_bytes,
+                            pfpp_stream_t stream);
+int pfpp_sinkhorn_train_bwd(const float* s, int64_t ld, int64_t n, float tau, int64_t max_iter, const int32_t* tgt, const double* pots,
+                            const float* ds_mat, float g, float* ds, int64_t ldg, void* workspace, int64_t workspace_bytes,
+                            pfpp_stream_t stream);
+int pfpp_match_gt_targets(const float* gt_pcs, int64_t N, const int64_t* src, const int32_t* row_piece, const int64_t* puz_row_off,
+                          int64_t B, int64_t max_rows, int32_t* tgt, pfpp_stream_t stream);
+int pfpp_match_normalize_halves_bwd(const float* x, const float* dy, float* dx, int64_t R, int64_t D, pfpp_stream_t stream);
+int64_t pfpp_match_cls_bce_workspace(void);
+int pfpp_match_cls_bce(const float* logits, int64_t ldl, const uint8_t* labels, int64_t N, float g, double* loss, float* dlogit,
+                       int64_t ldd, int64_t* counts, void* workspace, int64_t workspace_bytes, pfpp_stream_t stream);
+int pfpp_match_gather_raw(const float* feats, const int64_t* idx, int64_t N, int64_t R, int64_t C, float* out, pfpp_stream_t stream);
+int pfpp_match_scatter_raw(const float* in, const int64_t* idx, int64_t N, int64_t R, int64_t C, int accumulate, float* out,
+                           pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,8 +16,11 @@
 //  * fracture_labels_kernel — compute_label: distance to the nearest point of another piece of the same puzzle, squared
 //    distance in nn_dist_kernel's arithmetic with the target tiles in LDS, clamp(1e-12), sqrt, `<` in the reference's order.
 #include "pfpp_common.h"
+#include "sinkhorn_common.h"
 
 namespace {
+
+using namespace pfpp::sk;
 
 constexpr int MATCH_C = 128;        // PC_FEAT_DIM
 constexpr int MATCH_HALF = 256;     // AFF_FEAT_DIM / 2
@@ -120,32 +123,7 @@ __global__ __launch_bounds__(256) void match_normalize_halves_kernel(float* __re
 }
 
 // ------------------------------------------------------------------------------------------------ Sinkhorn, potential form
-// running (max, sum) of a log-sum-exp: one exp per element, no branch on the data.  The exponentials are fp32 (the reference's), the
-// running sum is fp64: at N' = 5,000 a column's sum is 64 pushes and 79 partials long, and a chain of that many fp32 roundings
-// is worth 4 - 5e-7 (relative) on the column's potential, more than the reference's pairwise fp32 summation loses.
-__device__ __forceinline__ void lse_push(float& m, double& s, float x) {
-  const float d = x - m;
-  const double e = (double)expf(-fabsf(d));
-  if (d > 0.0f) { s = s * e + 1.0; m = x; } else { s += e; }
-}
-__device__ __forceinline__ void lse_merge(float& m, double& s, float m2, double s2) {
-  const float nm = fmaxf(m, m2);
-  if (nm == -__builtin_huge_valf()) return;            // both empty
-  s = s * (double)expf(m - nm) + s2 * (double)expf(m2 - nm);
-  m = nm;
-}
-__device__ __forceinline__ float lse_value(float m, double s) { return m + logf((float)s); }
-
-constexpr int SK_ROWS = 64;       // rows per block of the column sweep
-
-// The potentials are fp64, the entries fp32.  u and v carry the magnitude of L (up to 1 / tau times the affinity, about 20): kept in
-// fp32 they would quantise every normalisation at ulp(20) / 2 = 9.5e-7, where the reference's rewrite form, whose entries are near
-// 0 after a normalisation, stays at 3 - 4e-7 from the float64 run.  L = s / tau is the reference's fp32 division; the entry (L - u_i) - v_j is formed in fp64 and
-// rounded once; the log-sum-exp itself runs in fp32 like the reference's.
-__device__ __forceinline__ float sk_entry(float s, float tau, double ui, double vj) {
-  return (float)(((double)(s / tau) - ui) - vj);
-}
-
+// (lse_push / lse_merge / lse_value, sk_entry and the block sizes: sinkhorn_common.h, shared with the training form)
 // u[i] += LSE_j((L_ij - u_i) - v_j) over the columns of other pieces; one wave per row
 __global__ __launch_bounds__(256) void sinkhorn_row_kernel(const float* __restrict__ s, int64_t ld, const int32_t* __restrict__ piece, int n,
                                                            float tau, double* __restrict__ u, const double* __restrict__ v) {
@@ -216,8 +194,6 @@ __global__ __launch_bounds__(256) void sinkhorn_col_partial_kernel(const float* 
 // column are nblk strided loads; one thread per column would leave 10 workgroups at N' = 2,492, each waiting on 2 x 39 of them).
 // Each quarter takes its maximum first, then its sum in block order; the four quarters
 // are folded in order through LDS.  Fixed order throughout: repeatable bit for bit.
-constexpr int CB_COLS = 64, CB_PARTS = 4;
-
 __global__ __launch_bounds__(256) void sinkhorn_col_combine_kernel(const float* __restrict__ pm, const double* __restrict__ ps, int n, int nblk,
                                                                    double* __restrict__ v) {
   __shared__ float qm[CB_PARTS][CB_COLS];

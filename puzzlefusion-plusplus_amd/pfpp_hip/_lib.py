@@ -345,6 +345,14 @@ SIGNATURES = {
     "pfpp_ptf_aggregate": [_p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p],
     "pfpp_attn_rows16": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
     "pfpp_layernorm128": [_p, _p, _p, _p, _i64, _i64, _f32, _p],
+    # ---- matcher head, training (csrc/matching_train.hip)
+    "pfpp_sinkhorn_train_fwd": [_p, _i64, _i64, _f32, _i64, _p, _p, _p, _p, _p, _p, _i64, _p],
+    "pfpp_sinkhorn_train_bwd": [_p, _i64, _i64, _f32, _i64, _p, _p, _p, _f32, _p, _i64, _p, _i64, _p],
+    "pfpp_match_gt_targets": [_p, _i64, _p, _p, _p, _i64, _i64, _p, _p],
+    "pfpp_match_normalize_halves_bwd": [_p, _p, _p, _i64, _i64, _p],
+    "pfpp_match_cls_bce": [_p, _i64, _p, _i64, _f32, _p, _p, _i64, _p, _p, _i64, _p],
+    "pfpp_match_gather_raw": [_p, _p, _i64, _i64, _i64, _p, _p],
+    "pfpp_match_scatter_raw": [_p, _p, _i64, _i64, _i64, C.c_int, _p, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
@@ -367,6 +375,8 @@ PLAIN = {
     "pfpp_bn_relu_bwd_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_mesh_vertex_graph_workspace": ([_p, _i64, _p], C.c_int64),
     "pfpp_sinkhorn_workspace": ([_i64], C.c_int64),
+    "pfpp_sinkhorn_train_workspace": ([_i64], C.c_int64),
+    "pfpp_match_cls_bce_workspace": ([], C.c_int64),
 }
 
 # struct name in include/pfpp.h (without the pfpp_ prefix) -> its mirror here; load() compares the sizes
