@@ -506,9 +506,30 @@ def sa_first_table(xyz: torch.Tensor, feats: torch.Tensor, w, bias: torch.Tensor
     return grouped_linear(xyz, t[1], feats, t[0], w, bias=bias)
 
 
-def sa_mlp3_fused(xyz: torch.Tensor, new_xyz: torch.Tensor, idx: torch.Tensor, w0, w1, w2, s0, t0, s1, t1, s2, t2) -> torch.Tensor:
+def _out_f32(out, rows: int, cols: int, device, who: str) -> torch.Tensor:
+    """the fp32 [rows, cols] result tensor of a wrapper: `out` if the caller gave one (checked), else a new one"""
+    if out is None:
+        return torch.empty((rows, cols), dtype=torch.float32, device=device)
+    _chk(out, torch.float32, "out")
+    if out.shape != (rows, cols):
+        raise ValueError(f"{who}: out must be [{rows}, {cols}]")
+    return out
+
+
+def _out_planes(out, rows: int, cols: int, device, who: str) -> "SplitAct":
+    """the split-f16 [rows, cols] result of a wrapper: `out` (a SplitAct or a (hi, lo) pair, checked) or a new SplitAct"""
+    if out is None:
+        return SplitAct.empty(rows, cols, device)
+    sp = out if isinstance(out, SplitAct) else SplitAct(*out)
+    _chk(sp.hi, torch.float16, "out.hi"); _chk(sp.lo, torch.float16, "out.lo")
+    if sp.hi.shape != (rows, cols) or sp.lo.shape != (rows, cols):
+        raise ValueError(f"{who}: out planes must be [{rows}, {cols}]")
+    return sp
+
+
+def sa_mlp3_fused(xyz: torch.Tensor, new_xyz: torch.Tensor, idx: torch.Tensor, w0, w1, w2, s0, t0, s1, t1, s2, t2, out=None) -> torch.Tensor:
     """grouping + three folded [conv, BN, ReLU] + max over nsample of a feature-less set-abstraction level in one kernel
-    (pfpp_sa_mlp3_fused); w* = packing.PW, s*/t* the folded BatchNorm scale / shift -> [F*S, C3]"""
+    (pfpp_sa_mlp3_fused); w* = packing.PW, s*/t* the folded BatchNorm scale / shift -> [F*S, C3] (written into `out` if given)"""
     _chk(xyz, torch.float32, "xyz"); _chk(new_xyz, torch.float32, "new_xyz"); _chk(idx, torch.int32, "idx")
     F, N, _ = xyz.shape
     _, S, ns = idx.shape
@@ -518,7 +539,7 @@ def sa_mlp3_fused(xyz: torch.Tensor, new_xyz: torch.Tensor, idx: torch.Tensor, w
         raise ValueError("sa_mlp3_fused: weight planes do not chain ([C1,8], [C2,C1], [C3,C2])")
     if (w0.scale, w1.scale, w2.scale) != (1.0, 1.0, 1.0):
         raise ValueError("sa_mlp3_fused reads the planes as they are: pack these weights with PW(w, prescale=False)")
-    out = torch.empty((F * S, w2.N), dtype=torch.float32, device=xyz.device)
+    out = _out_f32(out, F * S, w2.N, xyz.device, "sa_mlp3_fused")
     check(_lib.load().pfpp_sa_mlp3_fused(_ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(w0.hi), _ptr(w0.lo), _ptr(w1.hi), _ptr(w1.lo),
                                          _ptr(w2.hi), _ptr(w2.lo), _ptr(s0), _ptr(t0), _ptr(s1), _ptr(t1), _ptr(s2), _ptr(t2),
                                          _ptr(out), F, N, S, ns, w0.N, w1.N, w2.N, _stream()), "pfpp_sa_mlp3_fused")
@@ -531,13 +552,17 @@ def sa_mlp3_fused(xyz: torch.Tensor, new_xyz: torch.Tensor, idx: torch.Tensor, w
 PERSISTENT_WGS: Optional[int] = None
 
 
-def sa_pad_schedule(idx: torch.Tensor) -> torch.Tensor:
+def sa_pad_schedule(idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pfpp_sa_pad_schedule: idx [F, S, 64] ball-query indices -> int32 [3 F*S + 1]: the neighbourhoods with more than 32 live slots,
     then the others (each class ascending), the size of the first class at [F*S], then the live-slot counts by neighbourhood and in
-    schedule order"""
+    schedule order (written into `out` if given)"""
     _chk(idx, torch.int32, "idx")
     F, S, ns = idx.shape
-    sched = torch.empty((3 * F * S + 1,), dtype=torch.int32, device=idx.device)
+    if out is not None:
+        _chk(out, torch.int32, "out")
+        if out.shape != (3 * F * S + 1,):
+            raise ValueError("sa_pad_schedule: out must be int32 [3 F*S + 1]")
+    sched = out if out is not None else torch.empty((3 * F * S + 1,), dtype=torch.int32, device=idx.device)
     check(_lib.load().pfpp_sa_pad_schedule(_ptr(idx), F * S, ns, _ptr(sched), _stream()), "pfpp_sa_pad_schedule")
     return sched
 
@@ -640,9 +665,10 @@ def sa_train_stage(stage: int, xyz: torch.Tensor, new_xyz: torch.Tensor, feats: 
 
 
 def sa_mlp2_fused(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tensor, idx: torch.Tensor, w0, w1, s0, t0, s1, t1,
-                  as_planes: bool = False):
+                  as_planes: bool = False, out=None):
     """grouping + the first two folded [conv, BN, ReLU] of a set-abstraction level with input features in one kernel
-    (pfpp_sa_mlp2_fused) -> [F*S*ns, C2], the input of the level's third convolution; as_planes: a SplitAct (split-f16 planes)"""
+    (pfpp_sa_mlp2_fused) -> [F*S*ns, C2], the input of the level's third convolution; as_planes: a SplitAct (split-f16 planes);
+    out: the tensor (as_planes: a SplitAct or a (hi, lo) pair) to write into"""
     _chk(xyz, torch.float32, "xyz"); _chk(new_xyz, torch.float32, "new_xyz"); _chk(idx, torch.int32, "idx"); _chk(feats, torch.float32, "feats")
     F, N, _ = xyz.shape
     _, S, ns = idx.shape
@@ -654,20 +680,20 @@ def sa_mlp2_fused(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tensor,
     if (w0.scale, w1.scale) != (1.0, 1.0):
         raise ValueError("sa_mlp2_fused reads the planes as they are: pack these weights with PW(w, prescale=False)")
     if as_planes:
-        sp = SplitAct.empty(F * S * ns, w1.N, xyz.device)
+        sp = _out_planes(out, F * S * ns, w1.N, xyz.device, "sa_mlp2_fused")
         pc = _lib.PlanesC(sp.hi.data_ptr(), sp.lo.data_ptr(), 1.0)
         check(_lib.load().pfpp_sa_mlp2_fused_p(_ptr(feats), _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(w0.hi), _ptr(w0.lo), _ptr(w1.hi),
                                                _ptr(w1.lo), _ptr(s0), _ptr(t0), _ptr(s1), _ptr(t1), None, C.byref(pc), F, N, S, ns, D, w0.N,
                                                w1.N, _stream()), "pfpp_sa_mlp2_fused_p")
         return sp
-    out = torch.empty((F * S * ns, w1.N), dtype=torch.float32, device=xyz.device)
+    out = _out_f32(out, F * S * ns, w1.N, xyz.device, "sa_mlp2_fused")
     check(_lib.load().pfpp_sa_mlp2_fused(_ptr(feats), _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(w0.hi), _ptr(w0.lo), _ptr(w1.hi), _ptr(w1.lo),
                                          _ptr(s0), _ptr(t0), _ptr(s1), _ptr(t1), _ptr(out), F, N, S, ns, D, w0.N, w1.N, _stream()),
           "pfpp_sa_mlp2_fused")
     return out
 
 
-def sa_mlp2_table(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tensor, idx: torch.Tensor, w0, w1, s0, t0, s1, t1):
+def sa_mlp2_table(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tensor, idx: torch.Tensor, w0, w1, s0, t0, s1, t1, out=None):
     """sa_mlp2_fused(as_planes=True) with the first convolution taken per point (pfpp_sa_mlp2_table_p): u = sa_first_table without bias,
     then one launch that gathers u[idx], subtracts W_xyz . centroid inside the folded affine and runs the second layer -> SplitAct"""
     _chk(new_xyz, torch.float32, "new_xyz"); _chk(idx, torch.int32, "idx"); _chk(feats, torch.float32, "feats")
@@ -681,7 +707,7 @@ def sa_mlp2_table(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tensor,
     if (w0.scale, w1.scale) != (1.0, 1.0):
         raise ValueError("sa_mlp2_table reads the planes as they are: pack these weights with PW(w, prescale=False)")
     u = sa_first_table(xyz, feats, w0, None)
-    sp = SplitAct.empty(F * S * ns, w1.N, xyz.device)
+    sp = _out_planes(out, F * S * ns, w1.N, xyz.device, "sa_mlp2_table")
     pc = _lib.PlanesC(sp.hi.data_ptr(), sp.lo.data_ptr(), 1.0)
     check(_lib.load().pfpp_sa_mlp2_table_p(_ptr(u), _ptr(new_xyz), _ptr(idx), _ptr(w0.hi), _ptr(w0.lo), _ptr(w1.hi), _ptr(w1.lo), _ptr(s0),
                                            _ptr(t0), _ptr(s1), _ptr(t1), C.byref(pc), F, N, S, ns, D, w0.N, w1.N,
@@ -689,7 +715,7 @@ def sa_mlp2_table(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tensor,
     return sp
 
 
-def sa_table_planes(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tensor, idx: torch.Tensor, w0, s0, t0):
+def sa_table_planes(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tensor, idx: torch.Tensor, w0, s0, t0, out=None):
     """first folded [conv, BN, ReLU] of a level with features on every grouped row, from the per-point table (pfpp_sa_table_planes):
     grouped_linear(..., scale=s0, shift=t0, act="relu") as a SplitAct without the grouped matrix work"""
     _chk(new_xyz, torch.float32, "new_xyz"); _chk(idx, torch.int32, "idx"); _chk(feats, torch.float32, "feats")
@@ -700,7 +726,7 @@ def sa_table_planes(xyz: torch.Tensor, new_xyz: torch.Tensor, feats: torch.Tenso
     if feats.shape[:2] != (F, N) or w0.hi.shape != (w0.N, D + 8) or w0.scale != 1.0:
         raise ValueError("sa_table_planes: feats [F,N,D], w0 planes [C1, D+8] packed with PW(w, prescale=False)")
     u = sa_first_table(xyz, feats, w0, None)
-    sp = SplitAct.empty(F * S * ns, w0.N, xyz.device)
+    sp = _out_planes(out, F * S * ns, w0.N, xyz.device, "sa_table_planes")
     pc = _lib.PlanesC(sp.hi.data_ptr(), sp.lo.data_ptr(), 1.0)
     check(_lib.load().pfpp_sa_table_planes(_ptr(u), _ptr(new_xyz), _ptr(idx), _ptr(w0.hi), _ptr(w0.lo), _ptr(s0), _ptr(t0), C.byref(pc),
                                            F, N, S, ns, D, w0.N, _stream()), "pfpp_sa_table_planes")
