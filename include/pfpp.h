@@ -1335,6 +1335,36 @@ int pfpp_match_gather_raw(const float* feats, const int64_t* idx, int64_t N, int
 int pfpp_match_scatter_raw(const float* in, const int64_t* idx, int64_t N, int64_t R, int64_t C, int accumulate, float* out,
                            pfpp_stream_t stream);
 
+/* ---- matcher middle, training: the backward of the cross-attention layer tf_cross1 (Jigsaw_matching/model/jigsaw/attention_layer.py in
+ * .train() under autograd; csrc/matching_tf_train.hip).  The layer has no dropout (:15, :44, :86, :92 are commented out) and its
+ * norms are nn.LayerNorm: its training-time forward is the eval forward.  The linear layers' gradients go through pfpp_gemm in its
+ * exact-fp32 mode, the bias gradients through pfpp_colsum; these entries are the rest.
+ * pfpp_attn_rows16_train (:17-24 inside :47-69): pfpp_attn_rows16 with one more output, lse [rows, H] = log sum_j exp((q scale) . k_j)
+ * per (row, head).  out is bit for bit what pfpp_attn_rows16 writes, in both launch forms, chosen by the same size rule.
+ * pfpp_attn_rows16_bwd (autograd of :17-24 and of the head split / merge :55-69): dqkv [rows, 3 H 16] = dq | dk | dv from qkv, out and
+ * lse of the forward and dout [rows, H 16].  Two passes that recompute p = exp(s - lse), s formed as the forward forms it: dq with a
+ * query per lane over staged key tiles (D = dout . out per (row, head) is computed in its prologue and written to dvec, a workspace
+ * [rows, H]), then dk | dv with a key per lane over staged query tiles.  ds = p (dout . v - D), dq = sum_j ds k scale, dk = sum_i ds q
+ * scale, dv = sum_i p dout.  fp32 FMAs, no atomics, no cross-lane step: two runs agree bitwise; a sequence reads and writes its own
+ * rows; rows outside every sequence are not written.  The grid form is chosen by the sizes alone with the forward's rule.  dh = 16.
+ * pfpp_layernorm128_bwd (autograd of :73 and :95): x = the rows BEFORE the normalisation; mean and rstd are recomputed with
+ * pfpp_layernorm128's arithmetic.  With xh = (x - mean) rstd and g = dy gamma: dx (=, or += with accumulate_dx: the residual branch's
+ * gradient is already there) rstd (g - mean(g) - xh mean(g xh)); dgamma = sum_r dy xh and dbeta = sum_r dy are OVERWRITTEN, through one
+ * fp32 partial per wave of at most PFPP_LAYERNORM128_BWD_MAX_WG workgroups folded in fp64 in a fixed order (no atomics).  workspace:
+ * PFPP_LAYERNORM128_BWD_WS_FLOATS floats, whatever rows is.  dx may alias dy when accumulate_dx is 0.  rows = 0 writes nothing.  C = 128.
+ * pfpp_relu_bwd (autograd of F.relu :91): dh[r, c] = h[r, c] > 0 ? dh[r, c] : 0 in place over [rows, cols] with the row stride ld of
+ * both; h = the ReLU's output (or its input: the sign test is the same).                                                           */
+#define PFPP_LAYERNORM128_BWD_MAX_WG 256
+#define PFPP_LAYERNORM128_BWD_WS_FLOATS (PFPP_LAYERNORM128_BWD_MAX_WG * 4 * 2 * 128)
+int pfpp_attn_rows16_train(const float* qkv, float* out, float* lse, const int32_t* seq_off, const int32_t* seq_len, int64_t n_seq,
+                           int64_t max_len, int64_t H, int64_t dh, float scale, pfpp_stream_t stream);
+int pfpp_attn_rows16_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dvec /* workspace [rows, H] */,
+                         float* dqkv, const int32_t* seq_off, const int32_t* seq_len, int64_t n_seq, int64_t max_len, int64_t H,
+                         int64_t dh, float scale, pfpp_stream_t stream);
+int pfpp_layernorm128_bwd(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta, float* workspace,
+                          int64_t rows, int64_t C, float eps, int accumulate_dx, pfpp_stream_t stream);
+int pfpp_relu_bwd(const float* h, float* dh, int64_t rows, int64_t cols, int64_t ld, pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -353,6 +353,11 @@ SIGNATURES = {
     "pfpp_match_cls_bce": [_p, _i64, _p, _i64, _f32, _p, _p, _i64, _p, _p, _i64, _p],
     "pfpp_match_gather_raw": [_p, _p, _i64, _i64, _i64, _p, _p],
     "pfpp_match_scatter_raw": [_p, _p, _i64, _i64, _i64, C.c_int, _p, _p],
+    # ---- matcher middle, training (csrc/matching_tf_train.hip)
+    "pfpp_attn_rows16_train": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
+    "pfpp_attn_rows16_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
+    "pfpp_layernorm128_bwd": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, C.c_int, _p],
+    "pfpp_relu_bwd": [_p, _p, _i64, _i64, _i64, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
