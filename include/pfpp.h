@@ -1365,6 +1365,63 @@ int pfpp_layernorm128_bwd(const float* x, const float* dy, const float* gamma, f
                           int64_t rows, int64_t C, float eps, int accumulate_dx, pfpp_stream_t stream);
 int pfpp_relu_bwd(const float* h, float* dh, int64_t rows, int64_t cols, int64_t ld, pfpp_stream_t stream);
 
+/* ---- matcher middle, training: the point-transformer layer tf_self1 (attention_layer.py:159-225 in .train() under autograd;
+ * csrc/matching_ptf_train.hip) behind the projection GEMM and the two searches.  Its three norms are BatchNorm1d over the channels of
+ * [N, 16, C]: the training forward normalises with the statistics of all 16 N rows of the call (padded slots included, biased variance,
+ * eps) and moves the running buffers (momentum, unbiased variance).  q, k, v, xyz, idx_k, idx_v, ld as in pfpp_ptf_aggregate.
+ * pack: PFPP_PTF_TRAIN_FLOATS floats.  The caller fills the raw weights:
+ *   [0, 9) linear_p[0].weight, [12, 15) linear_p[0].bias, [36, 420) linear_p[3].weight [128][3], [420, 548) linear_p[3].bias,
+ *   [1060, 3108) linear_w[2].weight [16][128], [3108, 3124) linear_w[2].bias, [3188, 3444) linear_w[5].weight [16][16],
+ *   [3444, 3460) linear_w[5].bias;
+ * the entries write the rest: per BatchNorm scale = gamma rstd | shift = beta - mean scale | rstd | -mean rstd at 16 / 548 / 3124 (vectors
+ * of 3 in slots of 4, of 128, of 16), and the backward's means of dz | dz x hat at 3460 (BatchNorm(16)) and 3492 (BatchNorm(128)).
+ * Every per-channel sum is an fp64 partial per workgroup (at most PFPP_PTF_TRAIN_MAX_WG) in workspace (PFPP_PTF_TRAIN_WS_DOUBLES doubles,
+ * whatever N is), folded in a fixed order into sums (fp64, device): no atomics, two runs agree bitwise.  Nothing with N 16 128 elements
+ * is written; u, w, du are [N, 16, 16].  pre_dump (may be null; tests): the float32 values the launch compares with 0.
+ * Forward, in this order:
+ *   pfpp_ptf_train_bn3_stats    sums [6] = sum a | sum a^2, a = linear_p[0](g_p)
+ *   pfpp_ptf_train_bn_finalise  which = 0 (BatchNorm(3)), 1 (128), 2 (16); rows = 16 N: sums [2 C] -> pack, running buffers
+ *   pfpp_ptf_train_bn128_stats  sums [256] of r = x_k[ik] - x_q + p_r; pre_dump [N, 16, 3]
+ *   pfpp_ptf_train_tile         u [N, 16, 16] = linear_w[2](relu(bn(r))), sums [32]; pre_dump [N, 16, 128]
+ *   pfpp_ptf_train_finish       w [N, 16, 16] = the softmax weights, out [N, 128]; pre_dump [N, 16, 16]
+ * Backward of sum(out dout), in this order:
+ *   pfpp_ptf_train_bwd_w        dz2 [N, 16, 16]; sums [PFPP_PTF_TRAIN_BWD_W_SUMS] = dW5 [16][16] | db5 | sum dz2 = dbeta | sum dz2 x hat = dgamma
+ *   pfpp_ptf_train_bwd_u        du <- the input gradient of BatchNorm(16), IN PLACE over dz2; sums [.._BWD_U_SUMS] = dW2 [16][128] | dbeta [128] | dgamma [128]
+ *   pfpp_ptf_train_bwd_r        dqkv[:, 0:128] = dx_q; sums [.._BWD_R_SUMS] = dW3 [128][3] | db3 [128] | 27 moments over all rows with dz0 the
+ *                               gradient at the BatchNorm(3) output, xh0 its normalised input, d = g_p: sum dz0_m [3] | sum dz0_m xh0_m [3] |
+ *                               sum dz0_m d_l [3][3] | sum xh0_m d_l [3][3] | sum d_l [3]
+ *   pfpp_ptf_train_bwd_gather   dqkv[:, 128:256] = dx_k, [:, 256:384] = dx_v: row m sums the entries e = point 16 + slot of ent_k[off_k[m] ..
+ *                               off_k[m + 1]) (the slots whose idx_k is m; ascending) in that order, likewise for v; a row in no list gets zeros
+ * The gradients of linear_p[0].bias and linear_w[2].bias are zero in exact arithmetic (a batch-statistics BatchNorm follows) and are
+ * not computed.                                                                                                                    */
+#define PFPP_PTF_TRAIN_FLOATS 3748
+#define PFPP_PTF_TRAIN_MAX_WG 1024
+#define PFPP_PTF_TRAIN_BWD_W_SUMS 304
+#define PFPP_PTF_TRAIN_BWD_U_SUMS 2304
+#define PFPP_PTF_TRAIN_BWD_R_SUMS 539
+#define PFPP_PTF_TRAIN_WS_DOUBLES (PFPP_PTF_TRAIN_MAX_WG * PFPP_PTF_TRAIN_BWD_U_SUMS)
+int pfpp_ptf_train_bn3_stats(const float* xyz, const int32_t* idx_k, const float* pack, int64_t N, int64_t K, double* workspace, double* sums,
+                             pfpp_stream_t stream);
+int pfpp_ptf_train_bn_finalise(const double* sums, int64_t which, int64_t rows, const float* gamma, const float* beta, float eps,
+                               float momentum, float* running_mean, float* running_var, float* pack, pfpp_stream_t stream);
+int pfpp_ptf_train_bn128_stats(const float* q, const float* k, int64_t ld, const float* xyz, const int32_t* idx_k, const float* pack, int64_t N,
+                               int64_t C, int64_t K, double* workspace, double* sums, float* pre_dump, pfpp_stream_t stream);
+int pfpp_ptf_train_tile(const float* q, const float* k, int64_t ld, const float* xyz, const int32_t* idx_k, const float* pack, int64_t N,
+                        int64_t C, int64_t K, float* u, double* workspace, double* sums, float* pre_dump, pfpp_stream_t stream);
+int pfpp_ptf_train_finish(const float* v, int64_t ld, const float* xyz, const int32_t* idx_k, const int32_t* idx_v, const float* pack, int64_t N,
+                          int64_t C, int64_t K, const float* u, float* w, float* out, float* pre_dump, pfpp_stream_t stream);
+int pfpp_ptf_train_bwd_w(const float* dout, const float* w, const float* u, const float* v, int64_t ld, const float* xyz, const int32_t* idx_k,
+                         const int32_t* idx_v, float* pack, int64_t N, int64_t C, int64_t K, float* dz2, double* workspace, double* sums,
+                         float* pre_dump, pfpp_stream_t stream);
+int pfpp_ptf_train_bwd_u(const float* q, const float* k, int64_t ld, const float* xyz, const int32_t* idx_k, float* pack, int64_t N, int64_t C,
+                         int64_t K, const float* u, float* du, double* workspace, double* sums, float* pre_dump, pfpp_stream_t stream);
+int pfpp_ptf_train_bwd_r(const float* dout, const float* w, const float* du, const float* q, const float* k, int64_t ld, const float* xyz,
+                         const int32_t* idx_k, const float* pack, int64_t N, int64_t C, int64_t K, float* dqkv, int64_t ldg, double* workspace,
+                         double* sums, float* pre_dump, pfpp_stream_t stream);
+int pfpp_ptf_train_bwd_gather(const float* dout, const float* w, const float* du, const float* q, const float* k, int64_t ld, const float* xyz,
+                              const float* pack, int64_t N, int64_t C, int64_t K, const int64_t* off_k, const int32_t* ent_k,
+                              const int64_t* off_v, const int32_t* ent_v, float* dqkv, int64_t ldg, pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

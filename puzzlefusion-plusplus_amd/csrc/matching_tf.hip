@@ -18,11 +18,9 @@
 // No atomics anywhere: two runs agree bitwise.  This unit is compiled without contraction; fused operations are written as fmaf.
 #include "pfpp_common.h"
 #include "attn_rows16.h"
+#include "ptf_common.h"            // TF_C, TF_K, PW_*, AG_LDH: shared with the training unit
 
 namespace {
-
-constexpr int TF_C = 128;      // channels of the descriptors
-constexpr int TF_K = 16;       // neighbours
 
 // ------------------------------------------------------------------------------------------------ neighbours in feature space
 constexpr int FK_THREADS = 256;
@@ -170,24 +168,7 @@ __global__ __launch_bounds__(FK_THREADS) void feat_knn_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------ point-transformer aggregation
-// offsets into the packed weights (floats; include/pfpp.h PFPP_PTF_WEIGHT_FLOATS)
-constexpr int PW_P1W = 0;        // linear_p[0].weight [3][3]
-constexpr int PW_P1S = 12;       // BatchNorm(3) folded behind it: scale [3]
-constexpr int PW_P1T = 16;       //                                shift [3] (carries the bias of linear_p[0])
-constexpr int PW_P2W = 20;       // linear_p[3].weight [128][3]
-constexpr int PW_P2B = 404;      // linear_p[3].bias [128]
-constexpr int PW_A1 = 532;       // linear_w[0] (BatchNorm(128)): scale [128]
-constexpr int PW_C1 = 660;       //                               shift [128]
-constexpr int PW_W3 = 788;       // linear_w[2].weight [16][128]
-constexpr int PW_A2 = 2836;      // BatchNorm(16) folded behind it: scale [16]
-constexpr int PW_C2 = 2852;      //                                 shift [16] (carries the bias of linear_w[2])
-constexpr int PW_W4 = 2868;      // linear_w[5].weight [16][16]
-constexpr int PW_B4 = 3124;      // linear_w[5].bias [16]
-constexpr int PW_TOTAL = 3140;
-static_assert(PW_TOTAL == PFPP_PTF_WEIGHT_FLOATS, "include/pfpp.h and the kernel disagree on the packed weights");
-
 constexpr int AG_THREADS = 256;
-constexpr int AG_LDH = TF_C + 4;   // row stride of the relation tile: the four rows a wave reads at once start 4 banks apart
 
 __global__ __launch_bounds__(AG_THREADS) void ptf_aggregate_kernel(const float* __restrict__ xq, const float* __restrict__ xk,
                                                                    const float* __restrict__ xv, int64_t ld,

@@ -358,6 +358,16 @@ SIGNATURES = {
     "pfpp_attn_rows16_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
     "pfpp_layernorm128_bwd": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, C.c_int, _p],
     "pfpp_relu_bwd": [_p, _p, _i64, _i64, _i64, _p],
+    # ---- matcher middle, training: the point-transformer layer (csrc/matching_ptf_train.hip)
+    "pfpp_ptf_train_bn3_stats": [_p, _p, _p, _i64, _i64, _p, _p, _p],
+    "pfpp_ptf_train_bn_finalise": [_p, _i64, _i64, _p, _p, _f32, _f32, _p, _p, _p, _p],
+    "pfpp_ptf_train_bn128_stats": [_p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p],
+    "pfpp_ptf_train_tile": [_p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "pfpp_ptf_train_finish": [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "pfpp_ptf_train_bwd_w": [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "pfpp_ptf_train_bwd_u": [_p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p],
+    "pfpp_ptf_train_bwd_r": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p],
+    "pfpp_ptf_train_bwd_gather": [_p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
