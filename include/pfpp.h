@@ -55,11 +55,19 @@ int64_t pfpp_abi_sizeof(const char* name);
 int pfpp_device_cu_count(void);
 /* arithmetic of the attention FORWARD kernels for launches issued by the CALLING THREAD (thread-local like pfpp_last_error: the
  * library keeps no process-global mutable state) (pfpp_attn_dense*, pfpp_attn_blockdiag*; diffusers Attention,
- * attention.py:46-72 via denoiser_transformer.py:46-72): -1 = each kernel's default (split-f16 unless its PFPP_ATTN_* environment
- * switch says otherwise), 0 = exact fp32 matrix instructions (the range fallback of the sampler loops, pfpp_hip.ops.exact_fp32),
+ * attention.py:46-72 via denoiser_transformer.py:46-72): -1 = each kernel's default (split-f16 where there is such a kernel),
+ * 0 = exact fp32 matrix instructions (the range fallback of the sampler loops, pfpp_hip.ops.exact_fp32),
  * 1 = split-f16, 2 = single-pass fp16 (perf mode of BASELINE configs[4]; never a parity mode). */
 int pfpp_set_attention_mode(int mode);
 int pfpp_get_attention_mode(void);
+/* cross-check kernels of the attention entry points, thread-local like the mode and 0 by default: a mask of 1 = DENSE_F32 (dense
+ * attention: exact-fp32 kernels where split-f16 is the default, forward at mode -1 and backward), 2 = BD_F32 (block-diagonal: exact
+ * fp32 matrix instructions), 4 = BD_SCALAR (block-diagonal: the scalar kernels; a call with plane output keeps a matrix-instruction
+ * kernel), 8 = NO_SHORT (dense forward: the tile walker where the short-sequence kernel would run).  The product leaves it 0; the
+ * tests compare the kernels it selects with the default ones.  PFPP_EINVAL for an unknown bit.  No environment variable selects an
+ * attention kernel.  Every attention entry point names the kernel(s) it launched in pfpp_last_gemm_kernel(). */
+int pfpp_set_attention_cross_check(unsigned bits);
+unsigned pfpp_get_attention_cross_check(void);
 
 /* ---- a1: SE(3) rotate + valid-fragment gather ----------------------------
  * Denoiser._apply_rots (puzzlefusion_plusplus/denoiser/model/denoiser.py:55-63,
@@ -326,7 +334,9 @@ int pfpp_gemm_dw_group(const pfpp_dw_job* jobs, int32_t n_jobs, int64_t K, int32
 /* name of the kernel instantiation the calling thread's last pfpp_gemm, pfpp_gemm_planes, pfpp_gemm_dw_group, pfpp_gemm_grad or
  * pfpp_gemm_grad_group call launched ("" after a pfpp_gemm call that launched nothing; "+pl_reduce_kernel" appended where a slab
  * reduction followed): lets a profiler-side tool attribute event timings to kernel names.  gemm_pl_kernel's eighth field is a
- * constant 0 (a template parameter that no longer exists; the positions of the others are kept) */
+ * constant 0 (a template parameter that no longer exists; the positions of the others are kept).  pfpp_sa_train_stage and the
+ * attention entry points (pfpp_attn_dense*, pfpp_attn_blockdiag*) report here too: several launches of one call joined with '+' in
+ * launch order, "" after a refused call */
 const char* pfpp_last_gemm_kernel(void);
 
 /* ---- a4 + a5 + a6 fused, for a set-abstraction level without input features ---------------------------

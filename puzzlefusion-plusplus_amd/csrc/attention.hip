@@ -16,9 +16,10 @@
 // per-lane scalar multiply.  K/V tiles are shared by the 4 waves through a double-buffered LDS
 // stage (K rows padded to DH+4 floats: conflict-free 16-byte reads).
 // Sequences may have different lengths (seq_off / seq_len): padded fragments can be dropped.
-#include <stdlib.h>
-
 #include "pfpp_common.h"
+
+using pfpp::AttnKern;
+using pfpp_gemm_detail::report_no_kernel;
 
 namespace {
 
@@ -675,13 +676,49 @@ __global__ __launch_bounds__(256) void attn_dense_short_kernel(
 
 static int attn_dense_impl(const float* qkv, float* out, _Float16* out_hi, _Float16* out_lo, const int32_t* seq_off,
                            const int32_t* seq_len, const uint8_t* key_valid, int64_t kv_stride, int64_t n_seq,
-                           int64_t max_len, int64_t H, int64_t dh, float scale, pfpp_stream_t stream,
-                           float* lse = nullptr);
+                           int64_t max_len, int64_t H, int64_t dh, float scale, pfpp_stream_t stream, float* lse = nullptr) {
+  PFPP_REQUIRE(qkv && seq_off && seq_len, "null pointer");
+  PFPP_REQUIRE(n_seq >= 0 && max_len >= 1 && H >= 1, "bad sizes");
+  PFPP_SUPPORTED(dh == 64 || dh == 32, "dim_head must be 32 or 64");
+  PFPP_SUPPORTED(n_seq <= 65535 && H <= 65535, "too many sequences / heads for one launch");
+  PFPP_REQUIRE(pfpp::aligned16(qkv) && pfpp::aligned16(out) && pfpp::aligned16(out_hi) && pfpp::aligned16(out_lo),
+               "16-byte alignment");
+  if (n_seq == 0) return PFPP_OK;
+  const dim3 grid((unsigned)((max_len + 127) / 128), (unsigned)H, (unsigned)n_seq), block(256);
+  hipStream_t st = pfpp::as_stream(stream);
+  const int Hi = (int)H;
+#define ATTN_FWD(KERN, NAME) pfpp_launch_named<KERN>(NAME, grid, block, 0, st, qkv, out, out_hi, out_lo, seq_off, seq_len, key_valid, kv_stride, Hi, scale, lse)
+  switch (pfpp::choose_attn_dense_fwd((int)dh, max_len, H, n_seq, lse != nullptr, pfpp::attn_policy())) {
+    case AttnKern::DenseF16Single:
+      if (dh == 64) ATTN_FWD((attn_dense_f16_kernel<64, true>), "attn_dense_f16_kernel<64, true>");
+      else ATTN_FWD((attn_dense_f16_kernel<32, true>), "attn_dense_f16_kernel<32, true>");
+      break;
+    case AttnKern::DenseShort: {
+      constexpr size_t smem = (size_t)4 * (2 * 32 * (64 + 8) + 2 * 64 * (32 + 8)) * sizeof(_Float16) + (size_t)(4 * 32 * (64 + 4) + 8 * 32) * sizeof(float);
+      if (pfpp_allow_dyn_lds<attn_dense_short_kernel<64>>((int)smem) != hipSuccess) break;
+      const dim3 g32((unsigned)((max_len + 31) / 32), (unsigned)H, (unsigned)n_seq);
+      pfpp_launch_named<attn_dense_short_kernel<64>>("attn_dense_short_kernel<64>", g32, block, smem, st, qkv, out, out_hi, out_lo, seq_off, seq_len,
+                                                     key_valid, kv_stride, Hi, scale);
+      break;
+    }
+    case AttnKern::DenseF16:
+      if (dh == 64) ATTN_FWD((attn_dense_f16_kernel<64, false>), "attn_dense_f16_kernel<64, false>");
+      else ATTN_FWD((attn_dense_f16_kernel<32, false>), "attn_dense_f16_kernel<32, false>");
+      break;
+    default:
+      if (dh == 64) ATTN_FWD(attn_dense_kernel<64>, "attn_dense_kernel<64>");
+      else ATTN_FWD(attn_dense_kernel<32>, "attn_dense_kernel<32>");
+      break;
+  }
+#undef ATTN_FWD
+  return pfpp::check_launch("pfpp_attn_dense");
+}
 
 extern "C" int pfpp_attn_dense_train(const float* qkv, float* out, float* lse, const int32_t* seq_off,
                                      const int32_t* seq_len, const uint8_t* key_valid, int64_t kv_stride,
                                      int64_t n_seq, int64_t max_len, int64_t H, int64_t dh, float scale,
                                      pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(out && lse, "null pointer");
   return attn_dense_impl(qkv, out, nullptr, nullptr, seq_off, seq_len, key_valid, kv_stride, n_seq, max_len, H, dh,
                          scale, stream, lse);
@@ -692,6 +729,7 @@ extern "C" int pfpp_attn_dense_train_p(const float* qkv, float* out, float* lse,
                                        const int32_t* seq_len, const uint8_t* key_valid, int64_t kv_stride,
                                        int64_t n_seq, int64_t max_len, int64_t H, int64_t dh, float scale,
                                        const pfpp_planes* out_planes, pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(lse && (out || out_planes) && pfpp_planes_ok(out_planes), "null pointer");
   PFPP_REQUIRE(!out_planes || out_planes->scale == 1.0f, "forward planes are unscaled");
   return attn_dense_impl(qkv, out, out_planes ? (_Float16*)out_planes->hi : nullptr, out_planes ? (_Float16*)out_planes->lo : nullptr,
@@ -701,6 +739,7 @@ extern "C" int pfpp_attn_dense_train_p(const float* qkv, float* out, float* lse,
 extern "C" int pfpp_attn_dense(const float* qkv, float* out, const int32_t* seq_off, const int32_t* seq_len,
                                const uint8_t* key_valid, int64_t kv_stride, int64_t n_seq, int64_t max_len,
                                int64_t H, int64_t dh, float scale, pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(out, "null pointer");
   return attn_dense_impl(qkv, out, nullptr, nullptr, seq_off, seq_len, key_valid, kv_stride, n_seq, max_len, H, dh,
                          scale, stream);
@@ -710,62 +749,8 @@ extern "C" int pfpp_attn_dense_split(const float* qkv, void* out_hi, void* out_l
                                      const int32_t* seq_len, const uint8_t* key_valid, int64_t kv_stride,
                                      int64_t n_seq, int64_t max_len, int64_t H, int64_t dh, float scale,
                                      pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(out_hi && out_lo, "null pointer");
   return attn_dense_impl(qkv, nullptr, (_Float16*)out_hi, (_Float16*)out_lo, seq_off, seq_len, key_valid, kv_stride,
                          n_seq, max_len, H, dh, scale, stream);
-}
-
-static int attn_dense_impl(const float* qkv, float* out, _Float16* out_hi, _Float16* out_lo, const int32_t* seq_off,
-                           const int32_t* seq_len, const uint8_t* key_valid, int64_t kv_stride, int64_t n_seq,
-                           int64_t max_len, int64_t H, int64_t dh, float scale, pfpp_stream_t stream, float* lse) {
-  PFPP_REQUIRE(qkv && seq_off && seq_len, "null pointer");
-  PFPP_REQUIRE(n_seq >= 0 && max_len >= 1 && H >= 1, "bad sizes");
-  PFPP_SUPPORTED(dh == 64 || dh == 32, "dim_head must be 32 or 64");
-  PFPP_SUPPORTED(n_seq <= 65535 && H <= 65535, "too many sequences / heads for one launch");
-  PFPP_REQUIRE(pfpp::aligned16(qkv) && pfpp::aligned16(out) && pfpp::aligned16(out_hi) && pfpp::aligned16(out_lo),
-               "16-byte alignment");
-  if (n_seq == 0) return PFPP_OK;
-  const dim3 grid((unsigned)((max_len + 127) / 128), (unsigned)H, (unsigned)n_seq);
-  hipStream_t st = pfpp::as_stream(stream);
-  // split-f16 kernel (default for dim_head 64): 44.6 -> 26.3 us on the compacted (ragged) token list, where the longest
-  // sequence's walk over its key tiles is the critical path, and 226 -> 127 us on the all-slots form (32 x 500 keys, masked).
-  // (Its first version stored V^T with 2-byte LDS writes: 661 us there; pairs of keys as swizzled 4-byte words fixed it.)
-  // PFPP_ATTN_F16X3=0: the exact-fp32 MFMA kernel.
-  static const int f16_mode = getenv("PFPP_ATTN_F16X3") ? atoi(getenv("PFPP_ATTN_F16X3")) : 1;
-  const bool f16x3 = pfpp::attn_use_f16(f16_mode != 0);
-  if (pfpp::attn_mode() == 2 && !lse) {      // single-pass fp16 (inference only: the training forward keeps its fp32-grade statistics)
-    if (dh == 64)
-      hipLaunchKernelGGL((attn_dense_f16_kernel<64, true>), grid, dim3(256), 0, st, qkv, out, out_hi, out_lo, seq_off, seq_len,
-                         key_valid, kv_stride, (int)H, scale, lse);
-    else
-      hipLaunchKernelGGL((attn_dense_f16_kernel<32, true>), grid, dim3(256), 0, st, qkv, out, out_hi, out_lo, seq_off, seq_len,
-                         key_valid, kv_stride, (int)H, scale, lse);
-    return pfpp::check_launch("pfpp_attn_dense");
-  }
-  // few short sequences (one puzzle in flight): keys split over the waves of 32-query workgroups (attn_dense_short_kernel)
-  const char* short_env = getenv("PFPP_ATTN_SHORT_MAX");          // (read per call: the tests compare both kernels in one process)
-  const int short_max = short_env ? atoi(short_env) : 512;
-  if (dh == 64 && f16x3 && !lse && max_len <= short_max && (int64_t)grid.x * H * n_seq <= 64) {
-    constexpr size_t smem = (size_t)4 * (2 * 32 * (64 + 8) + 2 * 64 * (32 + 8)) * sizeof(_Float16) + (size_t)(4 * 32 * (64 + 4) + 8 * 32) * sizeof(float);
-    if (pfpp_allow_dyn_lds<attn_dense_short_kernel<64>>((int)smem) != hipSuccess) return pfpp::check_launch("pfpp_attn_dense");
-    const dim3 g32((unsigned)((max_len + 31) / 32), (unsigned)H, (unsigned)n_seq);
-    hipLaunchKernelGGL(attn_dense_short_kernel<64>, g32, dim3(256), smem, st, qkv, out, out_hi, out_lo, seq_off, seq_len, key_valid, kv_stride,
-                       (int)H, scale);
-    return pfpp::check_launch("pfpp_attn_dense");
-  }
-  if (dh == 64 && f16x3)
-    hipLaunchKernelGGL(attn_dense_f16_kernel<64>, grid, dim3(256), 0, st, qkv, out, out_hi, out_lo, seq_off, seq_len,
-                       key_valid, kv_stride, (int)H, scale, lse);
-  else if (dh == 32 && f16x3 && max_len >= 1024)
-    // the verifier's attention over thousands of candidate edges (100-fragment puzzles: 4,950 keys per query): 3 f16 MFMAs per
-    // 16-deep step instead of 8 fp32 ones; the 190 edges of the reference's 20-fragment puzzles keep the exact-fp32 kernel
-    hipLaunchKernelGGL(attn_dense_f16_kernel<32>, grid, dim3(256), 0, st, qkv, out, out_hi, out_lo, seq_off, seq_len,
-                       key_valid, kv_stride, (int)H, scale, lse);
-  else if (dh == 64)
-    hipLaunchKernelGGL(attn_dense_kernel<64>, grid, dim3(256), 0, st, qkv, out, out_hi, out_lo, seq_off, seq_len,
-                       key_valid, kv_stride, (int)H, scale, lse);
-  else
-    hipLaunchKernelGGL(attn_dense_kernel<32>, grid, dim3(256), 0, st, qkv, out, out_hi, out_lo, seq_off, seq_len,
-                       key_valid, kv_stride, (int)H, scale, lse);
-  return pfpp::check_launch("pfpp_attn_dense");
 }

@@ -14,8 +14,6 @@
 //
 // Block-diagonal self-attention (L <= 32 tokens per fragment): one wave per (fragment, head), all
 // five small products on the VALU out of LDS.
-#include <stdlib.h>
-
 #include "pfpp_common.h"
 
 namespace {
@@ -1334,8 +1332,12 @@ __global__ __launch_bounds__(64) void attn_blockdiag_f16_kernel(const float* __r
 
 }  // namespace
 
+using pfpp::AttnKern;
+using pfpp_gemm_detail::report_no_kernel;
+
 extern "C" int pfpp_attn_blockdiag_bwd(const float* qkv, const float* dout, float* dqkv, int64_t n_frag, int64_t L,
                                        int64_t H, int64_t dh, float scale, pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(dqkv, "null pointer");
   return pfpp_attn_blockdiag_bwd_p(qkv, dout, dqkv, n_frag, L, H, dh, scale, nullptr, stream);
 }
@@ -1343,39 +1345,89 @@ extern "C" int pfpp_attn_blockdiag_bwd(const float* qkv, const float* dout, floa
 extern "C" int pfpp_attn_blockdiag_bwd_p(const float* qkv, const float* dout, float* dqkv, int64_t n_frag, int64_t L,
                                          int64_t H, int64_t dh, float scale, const pfpp_planes* dqkv_planes,
                                          pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(qkv && dout && (dqkv || dqkv_planes) && pfpp_planes_ok(dqkv_planes), "null pointer");
   PFPP_SUPPORTED(dh == BD_DH, "dim_head != 64");
   PFPP_SUPPORTED(L >= 1 && L <= BD_L, "L outside [1, 32]");
   PFPP_REQUIRE(pfpp::aligned16(qkv) && pfpp::aligned16(dout), "16-byte alignment");
   const int64_t pairs = n_frag * H;
   if (pairs == 0) return PFPP_OK;
-  static const bool use_mfma = !(getenv("PFPP_ATTN_BD_MFMA") && atoi(getenv("PFPP_ATTN_BD_MFMA")) == 0);
-  // split-f16 contraction unless PFPP_ATTN_BD_F16X3=0 (then the exact fp32 matrix instructions)
-  static const bool use_f16 = !(getenv("PFPP_ATTN_BD_F16X3") && atoi(getenv("PFPP_ATTN_BD_F16X3")) == 0);
-  if (use_f16 && (use_mfma || dqkv_planes)) {
-    PFPP_SUPPORTED(pairs <= 0x7fffffff, "too many (fragment, head) pairs for one launch");
-    hipLaunchKernelGGL(attn_blockdiag_bwd_f16_kernel, dim3((unsigned)pairs), dim3(64), 0, pfpp::as_stream(stream), qkv, dout, dqkv,
-                       pairs, (int)L, (int)H, scale, pfpp_planes_arg(dqkv_planes));
-    return pfpp::check_launch("pfpp_attn_blockdiag_bwd");
+  const AttnKern kern = pfpp::choose_attn_blockdiag_bwd(dqkv_planes != nullptr, pfpp::attn_policy());
+  PFPP_SUPPORTED(kern != AttnKern::BdF16 || pairs <= 0x7fffffff, "too many (fragment, head) pairs for one launch");
+  hipStream_t st = pfpp::as_stream(stream);
+  switch (kern) {
+    case AttnKern::BdF16:
+      pfpp_launch_named<attn_blockdiag_bwd_f16_kernel>("attn_blockdiag_bwd_f16_kernel", dim3((unsigned)pairs), dim3(64), 0, st, qkv, dout, dqkv, pairs,
+                                                       (int)L, (int)H, scale, pfpp_planes_arg(dqkv_planes));
+      break;
+    case AttnKern::BdMfma:
+      pfpp_launch_named<attn_blockdiag_bwd_mfma_kernel>("attn_blockdiag_bwd_mfma_kernel", dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, qkv, dout,
+                                                        dqkv, pairs, (int)L, (int)H, scale, pfpp_planes_arg(dqkv_planes));
+      break;
+    default:
+      pfpp_launch_named<attn_blockdiag_bwd_kernel>("attn_blockdiag_bwd_kernel", dim3((unsigned)pairs), dim3(256),
+                                                   (size_t)(4 * L * BD_LD + 2 * L * (L + 1)) * sizeof(float), st, qkv, dout, dqkv, (int)L, (int)H, scale);
+      break;
   }
-  if (use_mfma || dqkv_planes) {
-    hipLaunchKernelGGL(attn_blockdiag_bwd_mfma_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, pfpp::as_stream(stream), qkv,
-                       dout, dqkv, pairs, (int)L, (int)H, scale, pfpp_planes_arg(dqkv_planes));
-    return pfpp::check_launch("pfpp_attn_blockdiag_bwd");
-  }
-  const size_t smem = (size_t)(4 * L * BD_LD + 2 * L * (L + 1)) * sizeof(float);
-  hipLaunchKernelGGL(attn_blockdiag_bwd_kernel, dim3((unsigned)pairs), dim3(256), smem, pfpp::as_stream(stream), qkv, dout,
-                     dqkv, (int)L, (int)H, scale);
-  return pfpp::check_launch(__func__);
+  return pfpp::check_launch("pfpp_attn_blockdiag_bwd");
 }
 
 extern "C" int pfpp_attn_dense_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
                                    float* dvec, float* dqkv, const int32_t* seq_off, const int32_t* seq_len,
                                    const uint8_t* key_valid, int64_t kv_stride, int64_t n_seq, int64_t max_len,
                                    int64_t H, int64_t dh, float scale, pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(dqkv, "null pointer");
   return pfpp_attn_dense_bwd_p(qkv, out, dout, lse, dvec, dqkv, seq_off, seq_len, key_valid, kv_stride, n_seq, max_len, H, dh,
                                scale, nullptr, stream);
+}
+
+// The longest report of an attention call is that of the three launches of pfpp_attn_dense_bwd_parts (sizeof counts each literal's
+// terminator: two of them stand for the '+' signs, the third ends the string).
+static_assert(sizeof("attn_dense_bwd_d_kernel<64>") + sizeof("attn_dense_bwd_dq_f16_kernel") + sizeof("attn_dense_bwd_dkv_f16_kernel") <=
+                  sizeof(pfpp_gemm_detail::pl::last_kernel), "pfpp_last_gemm_kernel's buffer is too short for the joined names");
+
+// pfpp_attn_dense_bwd_p (parts = 6 with d_from_dq: its dq pass also writes D = rowsum(dO . O) to dvec) and pfpp_attn_dense_bwd_parts
+// (bit 0: D by attn_dense_bwd_d_kernel) behind their pointer checks: one validation, reported under the caller's name `fn`, one
+// kernel choice, and the launches of the chosen passes.
+// (Both passes in one launch was built and measured twice — rounds 2 and 3: no gain, the longest sequence's workgroups of the two
+// passes then share SIMDs and each walks its tiles more slowly than alone — and removed in round 4.)
+static int attn_dense_bwd_impl(const char* fn, bool sizes_ok, const char* sizes_msg, int parts, bool d_from_dq, const float* qkv,
+                               const float* out, const float* dout, const float* lse, float* dvec, float* dqkv, const int32_t* seq_off,
+                               const int32_t* seq_len, const uint8_t* key_valid, int64_t kv_stride, int64_t n_seq, int64_t max_len, int64_t H,
+                               int64_t dh, float scale, const pfpp_planes* dqkv_planes, pfpp_stream_t stream) {
+  const auto fail = [fn](int code, const char* msg) {      // PFPP_REQUIRE / PFPP_SUPPORTED under the entry point's name
+    pfpp::set_error(code == PFPP_EINVAL ? "%s: %s" : "%s: unsupported: %s", fn, msg);
+    return code;
+  };
+  const AttnKern kern = pfpp::choose_attn_dense_bwd((int)dh, key_valid != nullptr, pfpp::attn_policy());
+  if (dqkv_planes && kern != AttnKern::DenseBwdF16)
+    return fail(PFPP_EUNSUPPORTED, "plane output of the attention backward needs the split-f16 passes (dim_head 64, no key mask)");
+  if (!sizes_ok) return fail(PFPP_EINVAL, sizes_msg);
+  if (dh != 64 && dh != 32) return fail(PFPP_EUNSUPPORTED, "dim_head must be 32 or 64");
+  if (n_seq > 65535 || H > 65535) return fail(PFPP_EUNSUPPORTED, "too many sequences / heads for one launch");
+  if (!(pfpp::aligned16(qkv) && pfpp::aligned16(out) && pfpp::aligned16(dout) && pfpp::aligned16(dqkv))) return fail(PFPP_EINVAL, "16-byte alignment");
+  if (n_seq == 0) return PFPP_OK;
+  const dim3 grid((unsigned)((max_len + 127) / 128), (unsigned)H, (unsigned)n_seq), block(256);
+  hipStream_t st = pfpp::as_stream(stream);
+  const int Hi = (int)H;
+  float* dq_d = d_from_dq ? dvec : nullptr;
+  const pfpp_planes_out po = pfpp_planes_arg(dqkv_planes);
+#define ATTN_BWD(KERN, NAME, ...) pfpp_launch_named<KERN>(NAME, grid, block, 0, st, __VA_ARGS__)
+  if ((parts & 1) && dh == 64) ATTN_BWD(attn_dense_bwd_d_kernel<64>, "attn_dense_bwd_d_kernel<64>", out, dout, dvec, seq_off, seq_len, Hi);
+  if ((parts & 1) && dh == 32) ATTN_BWD(attn_dense_bwd_d_kernel<32>, "attn_dense_bwd_d_kernel<32>", out, dout, dvec, seq_off, seq_len, Hi);
+  if (kern == AttnKern::DenseBwdF16) {
+    if (parts & 2) ATTN_BWD(attn_dense_bwd_dq_f16_kernel, "attn_dense_bwd_dq_f16_kernel", qkv, out, dout, lse, dq_d, dqkv, seq_off, seq_len, Hi, scale, po);
+    if (parts & 4) ATTN_BWD(attn_dense_bwd_dkv_f16_kernel, "attn_dense_bwd_dkv_f16_kernel", qkv, dout, lse, dvec, dqkv, seq_off, seq_len, Hi, scale, po);
+  } else if (dh == 64) {
+    if (parts & 2) ATTN_BWD(attn_dense_bwd_dq_kernel<64>, "attn_dense_bwd_dq_kernel<64>", qkv, out, dout, lse, dq_d, dqkv, seq_off, seq_len, key_valid, kv_stride, Hi, scale);
+    if (parts & 4) ATTN_BWD(attn_dense_bwd_dkv_kernel<64>, "attn_dense_bwd_dkv_kernel<64>", qkv, dout, lse, dvec, dqkv, seq_off, seq_len, key_valid, kv_stride, Hi, scale);
+  } else {
+    if (parts & 2) ATTN_BWD(attn_dense_bwd_dq_kernel<32>, "attn_dense_bwd_dq_kernel<32>", qkv, out, dout, lse, dq_d, dqkv, seq_off, seq_len, key_valid, kv_stride, Hi, scale);
+    if (parts & 4) ATTN_BWD(attn_dense_bwd_dkv_kernel<32>, "attn_dense_bwd_dkv_kernel<32>", qkv, dout, lse, dvec, dqkv, seq_off, seq_len, key_valid, kv_stride, Hi, scale);
+  }
+#undef ATTN_BWD
+  return pfpp::check_launch(fn);
 }
 
 extern "C" int pfpp_attn_dense_bwd_p(const float* qkv, const float* out, const float* dout, const float* lse,
@@ -1383,43 +1435,11 @@ extern "C" int pfpp_attn_dense_bwd_p(const float* qkv, const float* out, const f
                                      const uint8_t* key_valid, int64_t kv_stride, int64_t n_seq, int64_t max_len,
                                      int64_t H, int64_t dh, float scale, const pfpp_planes* dqkv_planes,
                                      pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(qkv && out && dout && lse && dvec && (dqkv || dqkv_planes) && seq_off && seq_len && pfpp_planes_ok(dqkv_planes),
                "null pointer");
-  static const int f16_mode_p = getenv("PFPP_ATTN_F16X3") ? atoi(getenv("PFPP_ATTN_F16X3")) : 1;
-  PFPP_SUPPORTED(!dqkv_planes || (dh == 64 && f16_mode_p >= 1 && key_valid == nullptr),
-                 "plane output of the attention backward needs the split-f16 passes (dim_head 64, no key mask)");
-  const pfpp_planes_out po = pfpp_planes_arg(dqkv_planes);
-  PFPP_REQUIRE(n_seq >= 0 && max_len >= 1 && H >= 1, "bad sizes");
-  PFPP_SUPPORTED(dh == 64 || dh == 32, "dim_head must be 32 or 64");
-  PFPP_SUPPORTED(n_seq <= 65535 && H <= 65535, "too many sequences / heads for one launch");
-  PFPP_REQUIRE(pfpp::aligned16(qkv) && pfpp::aligned16(out) && pfpp::aligned16(dout) && pfpp::aligned16(dqkv),
-               "16-byte alignment");
-  if (n_seq == 0) return PFPP_OK;
-  const dim3 grid((unsigned)((max_len + 127) / 128), (unsigned)H, (unsigned)n_seq);
-  hipStream_t st = pfpp::as_stream(stream);
-  // split-f16 passes for the unmasked (ragged) launches, like pfpp_attn_dense (PFPP_ATTN_F16X3: 0 never, 1 unmasked, 2 -)
-  static const int f16_mode = getenv("PFPP_ATTN_F16X3") ? atoi(getenv("PFPP_ATTN_F16X3")) : 1;
-  if (dh == 64 && f16_mode >= 1 && key_valid == nullptr) {
-    // (both passes in one launch was built and measured twice — rounds 2 and 3: no gain, the longest sequence's workgroups of the two
-    // passes then share SIMDs and each walks its tiles more slowly than alone — and removed in round 4)
-    hipLaunchKernelGGL(attn_dense_bwd_dq_f16_kernel, grid, dim3(256), 0, st, qkv, out, dout, lse, dvec, dqkv, seq_off, seq_len,
-                       (int)H, scale, po);
-    hipLaunchKernelGGL(attn_dense_bwd_dkv_f16_kernel, grid, dim3(256), 0, st, qkv, dout, lse, dvec, dqkv, seq_off, seq_len,
-                       (int)H, scale, po);
-    return pfpp::check_launch("pfpp_attn_dense_bwd");
-  }
-  if (dh == 64) {
-    hipLaunchKernelGGL(attn_dense_bwd_dq_kernel<64>, grid, dim3(256), 0, st, qkv, out, dout, lse, dvec, dqkv, seq_off,
-                       seq_len, key_valid, kv_stride, (int)H, scale);
-    hipLaunchKernelGGL(attn_dense_bwd_dkv_kernel<64>, grid, dim3(256), 0, st, qkv, dout, lse, dvec, dqkv, seq_off,
-                       seq_len, key_valid, kv_stride, (int)H, scale);
-  } else {
-    hipLaunchKernelGGL(attn_dense_bwd_dq_kernel<32>, grid, dim3(256), 0, st, qkv, out, dout, lse, dvec, dqkv, seq_off,
-                       seq_len, key_valid, kv_stride, (int)H, scale);
-    hipLaunchKernelGGL(attn_dense_bwd_dkv_kernel<32>, grid, dim3(256), 0, st, qkv, dout, lse, dvec, dqkv, seq_off,
-                       seq_len, key_valid, kv_stride, (int)H, scale);
-  }
-  return pfpp::check_launch(__func__);
+  return attn_dense_bwd_impl(__func__, n_seq >= 0 && max_len >= 1 && H >= 1, "bad sizes", 6, true, qkv, out, dout, lse, dvec, dqkv, seq_off, seq_len,
+                             key_valid, kv_stride, n_seq, max_len, H, dh, scale, dqkv_planes, stream);
 }
 
 // The same backward in separately launchable parts (bit 0: D = rowsum(dO . O) -> dvec, bit 1: dq, bit 2: dk/dv), so that a
@@ -1428,46 +1448,16 @@ extern "C" int pfpp_attn_dense_bwd_parts(const float* qkv, const float* out, con
                                          float* dvec, float* dqkv, const int32_t* seq_off, const int32_t* seq_len,
                                          const uint8_t* key_valid, int64_t kv_stride, int64_t n_seq, int64_t max_len,
                                          int64_t H, int64_t dh, float scale, int parts, pfpp_stream_t stream) {
+  report_no_kernel();
   PFPP_REQUIRE(qkv && out && dout && lse && dvec && dqkv && seq_off && seq_len, "null pointer");
-  PFPP_REQUIRE(n_seq >= 0 && max_len >= 1 && H >= 1 && parts >= 1 && parts <= 7, "bad sizes / parts");
-  PFPP_SUPPORTED(dh == 64 || dh == 32, "dim_head must be 32 or 64");
-  PFPP_SUPPORTED(n_seq <= 65535 && H <= 65535, "too many sequences / heads for one launch");
-  PFPP_REQUIRE(pfpp::aligned16(qkv) && pfpp::aligned16(out) && pfpp::aligned16(dout) && pfpp::aligned16(dqkv),
-               "16-byte alignment");
-  if (n_seq == 0) return PFPP_OK;
-  const dim3 grid((unsigned)((max_len + 127) / 128), (unsigned)H, (unsigned)n_seq);
-  hipStream_t st = pfpp::as_stream(stream);
-  const int Hi = (int)H;
-  static const int f16_mode = getenv("PFPP_ATTN_F16X3") ? atoi(getenv("PFPP_ATTN_F16X3")) : 1;
-  if (dh == 64 && f16_mode >= 1 && key_valid == nullptr) {      // same kernel choice as pfpp_attn_dense_bwd
-    if (parts & 1) hipLaunchKernelGGL(attn_dense_bwd_d_kernel<64>, grid, dim3(256), 0, st, out, dout, dvec, seq_off, seq_len, Hi);
-    const pfpp_planes_out none = pfpp_planes_arg(nullptr);
-    if (parts & 2) hipLaunchKernelGGL(attn_dense_bwd_dq_f16_kernel, grid, dim3(256), 0, st, qkv, out, dout, lse, (float*)nullptr, dqkv,
-                                      seq_off, seq_len, Hi, scale, none);
-    if (parts & 4) hipLaunchKernelGGL(attn_dense_bwd_dkv_f16_kernel, grid, dim3(256), 0, st, qkv, dout, lse, dvec, dqkv, seq_off,
-                                      seq_len, Hi, scale, none);
-    return pfpp::check_launch(__func__);
-  }
-  if (dh == 64) {
-    if (parts & 1) hipLaunchKernelGGL(attn_dense_bwd_d_kernel<64>, grid, dim3(256), 0, st, out, dout, dvec, seq_off, seq_len, Hi);
-    if (parts & 2) hipLaunchKernelGGL(attn_dense_bwd_dq_kernel<64>, grid, dim3(256), 0, st, qkv, out, dout, lse, (float*)nullptr, dqkv,
-                                      seq_off, seq_len, key_valid, kv_stride, Hi, scale);
-    if (parts & 4) hipLaunchKernelGGL(attn_dense_bwd_dkv_kernel<64>, grid, dim3(256), 0, st, qkv, dout, lse, dvec, dqkv, seq_off,
-                                      seq_len, key_valid, kv_stride, Hi, scale);
-  } else {
-    if (parts & 1) hipLaunchKernelGGL(attn_dense_bwd_d_kernel<32>, grid, dim3(256), 0, st, out, dout, dvec, seq_off, seq_len, Hi);
-    if (parts & 2) hipLaunchKernelGGL(attn_dense_bwd_dq_kernel<32>, grid, dim3(256), 0, st, qkv, out, dout, lse, (float*)nullptr, dqkv,
-                                      seq_off, seq_len, key_valid, kv_stride, Hi, scale);
-    if (parts & 4) hipLaunchKernelGGL(attn_dense_bwd_dkv_kernel<32>, grid, dim3(256), 0, st, qkv, dout, lse, dvec, dqkv, seq_off,
-                                      seq_len, key_valid, kv_stride, Hi, scale);
-  }
-  return pfpp::check_launch(__func__);
+  return attn_dense_bwd_impl(__func__, n_seq >= 0 && max_len >= 1 && H >= 1 && parts >= 1 && parts <= 7, "bad sizes / parts", parts, false, qkv, out,
+                             dout, lse, dvec, dqkv, seq_off, seq_len, key_valid, kv_stride, n_seq, max_len, H, dh, scale, nullptr, stream);
 }
 
 // internal: the split-f16 forward of the per-fragment attention (called by pfpp_attn_blockdiag / _split in transformer_ops.hip)
 int pfpp_attn_blockdiag_f16_launch(const float* qkv, float* out, void* out_hi, void* out_lo, int64_t pairs, int64_t L, int64_t H, float scale,
                                    hipStream_t st) {
-  hipLaunchKernelGGL(attn_blockdiag_f16_kernel, dim3((unsigned)pairs), dim3(64), 0, st, qkv, out, (_Float16*)out_hi, (_Float16*)out_lo, pairs,
-                     (int)L, (int)H, scale);
+  pfpp_launch_named<attn_blockdiag_f16_kernel>("attn_blockdiag_f16_kernel", dim3((unsigned)pairs), dim3(64), 0, st, qkv, out, (_Float16*)out_hi,
+                                               (_Float16*)out_lo, pairs, (int)L, (int)H, scale);
   return pfpp::check_launch("pfpp_attn_blockdiag");
 }

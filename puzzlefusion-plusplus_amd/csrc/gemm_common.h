@@ -3,9 +3,6 @@
 // residual / max over row groups).  Accumulator layout of a 32x32 MFMA tile (dtype independent on
 // gfx950): element e of lane l is C[row = (e&3) + 8*(e>>2) + 4*(l>>5)][col = l&31].
 #pragma once
-#include <stdarg.h>
-#include <string.h>
-
 #include "pfpp_common.h"
 
 namespace pfpp_gemm_detail {
@@ -45,22 +42,7 @@ struct GemmP {
   int reserved;   // always 0 (once a mask of lab ablation switches): kept so that the layout, and with it every kernel's argument offsets, stays as it was
 };
 
-// template instantiation (and "+pl_reduce_kernel" where a slab reduction follows) of the most recent GEMM or set-abstraction
-// stage launch of this thread, as a kernel trace prints it: written by every launcher of gemm.hip, gemm_pl.hip, gemm_grad.hip and
-// pfpp_sa_train_stage (sa_train.hip), read by pfpp_last_gemm_kernel (gemm_pl.hip)
-namespace pl { extern thread_local char last_kernel[96]; }
-// A launcher formats the name of its instantiation once (a function-local static) and copies it per launch: no printf on the
-// launch path.  80 characters + the longest suffix (17) fit last_kernel.
-struct KernelName {
-  char s[80];
-  explicit KernelName(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(s, sizeof(s), fmt, ap);
-    va_end(ap);
-  }
-};
-inline void report_kernel(const KernelName& name, const char* suffix = "") { strcpy(stpcpy(pl::last_kernel, name.s), suffix); }
+// pl::last_kernel, KernelName and report_kernel (what pfpp_last_gemm_kernel reports): pfpp_common.h
 
 __device__ __forceinline__ float act_apply(float v, int act) {
   switch (act) {

@@ -24,10 +24,10 @@ int check_launch(const char* what) {
   return PFPP_OK;
 }
 
-// arithmetic mode of the attention kernels for launches issued by THIS thread (pfpp_set_attention_mode): like the error text, state
+// kernel selection of the attention entry points for launches issued by THIS thread (csrc/attn_choice.h): like the error text, state
 // of the calling thread, not of the process - two host threads driving two streams never see each other's setting
-static thread_local int g_attn_mode = -1;
-int attn_mode() { return g_attn_mode; }
+static thread_local AttnPolicy g_attn = {-1, 0u};
+AttnPolicy attn_policy() { return g_attn; }
 
 }  // namespace pfpp
 
@@ -36,11 +36,22 @@ extern "C" int pfpp_set_attention_mode(int mode) {
     pfpp::set_error("pfpp_set_attention_mode: mode must be -1 (defaults), 0 (exact fp32), 1 (split-f16) or 2 (single-pass fp16)");
     return PFPP_EINVAL;
   }
-  pfpp::g_attn_mode = mode;
+  pfpp::g_attn.mode = mode;
   return PFPP_OK;
 }
 
-extern "C" int pfpp_get_attention_mode(void) { return pfpp::g_attn_mode; }
+extern "C" int pfpp_get_attention_mode(void) { return pfpp::g_attn.mode; }
+
+extern "C" int pfpp_set_attention_cross_check(unsigned bits) {
+  if (bits & ~pfpp::ATTN_X_ALL) {
+    pfpp::set_error("pfpp_set_attention_cross_check: unknown bits (1 DENSE_F32, 2 BD_F32, 4 BD_SCALAR, 8 NO_SHORT)");
+    return PFPP_EINVAL;
+  }
+  pfpp::g_attn.cross = bits;
+  return PFPP_OK;
+}
+
+extern "C" unsigned pfpp_get_attention_cross_check(void) { return pfpp::g_attn.cross; }
 
 extern "C" int pfpp_version(void) { return PFPP_ABI_VERSION; }
 

@@ -3,8 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 
+#include "attn_choice.h"
 #include "pfpp.h"
 
 #define PFPP_WAVE 64
@@ -24,14 +27,47 @@ inline hipStream_t as_stream(pfpp_stream_t s) {
 // after a launch: turn a launch failure into PFPP_EHIP
 int check_launch(const char* what);
 
-// process-wide arithmetic mode of the attention kernels (pfpp_set_attention_mode): -1 = each kernel's default (environment),
-// 0 = exact fp32 matrix instructions, 1 = split-f16, 2 = single-pass fp16 (perf mode, never for parity)
-int attn_mode();
-inline bool attn_use_f16(bool env_default) { const int m = attn_mode(); return m < 0 ? env_default : m >= 1; }
+// kernel selection of the attention entry points for launches issued by THIS thread (attn_choice.h): the arithmetic mode of
+// pfpp_set_attention_mode and the cross-check bits of pfpp_set_attention_cross_check
+AttnPolicy attn_policy();
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace pfpp
+
+// Template instantiation(s) of the most recent GEMM, set-abstraction stage or attention call of this thread, as a kernel trace prints
+// them: written by every launcher of gemm.hip, gemm_pl.hip, gemm_grad.hip, pfpp_sa_train_stage (sa_train.hip) and the attention entry
+// points, read by pfpp_last_gemm_kernel (gemm_pl.hip).  A call that launches nothing (empty input, rejected arguments) reports "".
+namespace pfpp_gemm_detail {
+namespace pl { extern thread_local char last_kernel[96]; }
+// A launcher formats the name of its instantiation once (a function-local static) and copies it per launch: no printf on the
+// launch path.  80 characters + the longest suffix (17) fit last_kernel.
+struct KernelName {
+  char s[80];
+  explicit KernelName(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(s, sizeof(s), fmt, ap);
+    va_end(ap);
+  }
+};
+inline void report_kernel(const KernelName& name, const char* suffix = "") { strcpy(stpcpy(pl::last_kernel, name.s), suffix); }
+inline void report_no_kernel() { pl::last_kernel[0] = 0; }
+// one launch of a call that may launch several kernels (the attention entries): after report_no_kernel() the names join with '+' in
+// launch order.  `name` is a literal; the caller static_asserts that its longest sequence fits last_kernel.
+inline void report_kernel_also(const char* name) {
+  char* end = pl::last_kernel + strlen(pl::last_kernel);
+  if (end != pl::last_kernel) *end++ = '+';
+  strcpy(end, name);
+}
+}  // namespace pfpp_gemm_detail
+
+// launch KERN and report it under `name`: its instantiation as a kernel trace prints it (defaulted template arguments written out)
+template <auto KERN, typename... Args>
+inline void pfpp_launch_named(const char* name, dim3 grid, dim3 block, size_t smem, hipStream_t st, Args... args) {
+  pfpp_gemm_detail::report_kernel_also(name);
+  hipLaunchKernelGGL(KERN, grid, block, smem, st, args...);
+}
 
 // internal (attention_bwd.hip): split-f16 forward of the per-fragment attention, launched by pfpp_attn_blockdiag / _split
 int pfpp_attn_blockdiag_f16_launch(const float* qkv, float* out, void* out_hi, void* out_lo, int64_t pairs, int64_t L, int64_t H, float scale,

@@ -620,21 +620,6 @@ static int layernorm_impl(const float* x, float* y, _Float16* y_hi, _Float16* y_
 }
 
 static int attn_blockdiag_impl(const float* qkv, float* out, _Float16* out_hi, _Float16* out_lo, int64_t n_frag,
-                               int64_t L, int64_t H, int64_t dh, float scale, pfpp_stream_t stream);
-
-extern "C" int pfpp_attn_blockdiag(const float* qkv, float* out, int64_t n_frag, int64_t L,
-                                   int64_t H, int64_t dh, float scale, pfpp_stream_t stream) {
-  PFPP_REQUIRE(qkv && out, "null pointer");
-  return attn_blockdiag_impl(qkv, out, nullptr, nullptr, n_frag, L, H, dh, scale, stream);
-}
-
-extern "C" int pfpp_attn_blockdiag_split(const float* qkv, void* out_hi, void* out_lo, int64_t n_frag, int64_t L,
-                                         int64_t H, int64_t dh, float scale, pfpp_stream_t stream) {
-  PFPP_REQUIRE(qkv && out_hi && out_lo, "null pointer");
-  return attn_blockdiag_impl(qkv, nullptr, (_Float16*)out_hi, (_Float16*)out_lo, n_frag, L, H, dh, scale, stream);
-}
-
-static int attn_blockdiag_impl(const float* qkv, float* out, _Float16* out_hi, _Float16* out_lo, int64_t n_frag,
                                int64_t L, int64_t H, int64_t dh, float scale, pfpp_stream_t stream) {
   PFPP_SUPPORTED(dh == AB_DH, "dim_head != 64");
   PFPP_SUPPORTED(L >= 1 && L <= AB_LMAX, "L outside [1, 32]");
@@ -642,20 +627,34 @@ static int attn_blockdiag_impl(const float* qkv, float* out, _Float16* out_hi, _
                "16-byte alignment");
   const int64_t pairs = n_frag * H;
   if (pairs == 0) return PFPP_OK;
-  static const bool use_mfma = !(getenv("PFPP_ATTN_BD_MFMA") && atoi(getenv("PFPP_ATTN_BD_MFMA")) == 0);
-  // split-f16 contraction (attention_bwd.hip: attn_blockdiag_f16_kernel) unless PFPP_ATTN_BD_F16X3=0 (then the exact fp32 matrix instructions)
-  static const bool use_f16 = !(getenv("PFPP_ATTN_BD_F16X3") && atoi(getenv("PFPP_ATTN_BD_F16X3")) == 0);
-  if (use_mfma && pfpp::attn_use_f16(use_f16) && dh == 64 && pairs <= 0x7fffffff)
-    return pfpp_attn_blockdiag_f16_launch(qkv, out, out_hi, out_lo, pairs, L, H, scale, pfpp::as_stream(stream));
-  if (use_mfma) {
-    hipLaunchKernelGGL(attn_blockdiag_mfma_kernel, dim3(blocks_for(pairs, 4)), dim3(256), 0, pfpp::as_stream(stream), qkv, out,
-                       out_hi, out_lo, pairs, (int)L, (int)H, scale);
-    return pfpp::check_launch("pfpp_attn_blockdiag");
+  hipStream_t st = pfpp::as_stream(stream);
+  switch (pfpp::choose_attn_blockdiag_fwd(pairs, pfpp::attn_policy())) {
+    case pfpp::AttnKern::BdF16:      // the split-f16 contraction (attention_bwd.hip: attn_blockdiag_f16_kernel)
+      return pfpp_attn_blockdiag_f16_launch(qkv, out, out_hi, out_lo, pairs, L, H, scale, st);
+    case pfpp::AttnKern::BdMfma:     // the exact fp32 matrix instructions
+      pfpp_launch_named<attn_blockdiag_mfma_kernel>("attn_blockdiag_mfma_kernel", dim3(blocks_for(pairs, 4)), dim3(256), 0, st, qkv, out, out_hi, out_lo,
+                                                    pairs, (int)L, (int)H, scale);
+      break;
+    default:
+      pfpp_launch_named<attn_blockdiag_kernel>("attn_blockdiag_kernel", dim3(blocks_for(pairs, 4)), dim3(256), 4 * 2 * AB_LMAX * AB_DH * sizeof(float), st,
+                                               qkv, out, out_hi, out_lo, pairs, (int)L, (int)H, scale);
+      break;
   }
-  const size_t smem = 4 * 2 * AB_LMAX * AB_DH * sizeof(float);
-  hipLaunchKernelGGL(attn_blockdiag_kernel, dim3(blocks_for(pairs, 4)), dim3(256), smem,
-                     pfpp::as_stream(stream), qkv, out, out_hi, out_lo, pairs, (int)L, (int)H, scale);
   return pfpp::check_launch("pfpp_attn_blockdiag");
+}
+
+extern "C" int pfpp_attn_blockdiag(const float* qkv, float* out, int64_t n_frag, int64_t L,
+                                   int64_t H, int64_t dh, float scale, pfpp_stream_t stream) {
+  pfpp_gemm_detail::report_no_kernel();
+  PFPP_REQUIRE(qkv && out, "null pointer");
+  return attn_blockdiag_impl(qkv, out, nullptr, nullptr, n_frag, L, H, dh, scale, stream);
+}
+
+extern "C" int pfpp_attn_blockdiag_split(const float* qkv, void* out_hi, void* out_lo, int64_t n_frag, int64_t L,
+                                         int64_t H, int64_t dh, float scale, pfpp_stream_t stream) {
+  pfpp_gemm_detail::report_no_kernel();
+  PFPP_REQUIRE(qkv && out_hi && out_lo, "null pointer");
+  return attn_blockdiag_impl(qkv, nullptr, (_Float16*)out_hi, (_Float16*)out_lo, n_frag, L, H, dh, scale, stream);
 }
 
 extern "C" int pfpp_softmax_rows(float* S, const uint8_t* key_valid, int64_t rows_total,

@@ -215,6 +215,7 @@ SIGNATURES = {
     "pfpp_tlayers_fwd": [C.POINTER(TlayersArgs), _i32, _i32, _p],
     "pfpp_tlayers_bwd": [C.POINTER(TlayersArgs), _i32, _i32, _p, _p],
     "pfpp_set_attention_mode": [C.c_int],
+    "pfpp_set_attention_cross_check": [C.c_uint],
     "pfpp_se3_rotate_gather": [_p, _p, _p, _p, _i64, _i64, _p],
     "pfpp_pose_apply": [_p, _p, _p, _p, _i64, _i64, C.c_int, _p],
     "pfpp_fps": [_p, _p, _p, _i64, _i64, _i64, _p],
@@ -377,6 +378,7 @@ PLAIN = {
     "pfpp_last_gemm_kernel": ([], C.c_char_p),
     "pfpp_device_cu_count": ([], C.c_int),
     "pfpp_get_attention_mode": ([], C.c_int),
+    "pfpp_get_attention_cross_check": ([], C.c_uint),
     "pfpp_ada_linear_bwd_scratch_floats": ([_i64, _i64], C.c_int64),
     "pfpp_token_features_t_cols": ([_i64, _i64], C.c_int64),
     "pfpp_tlayers_fwd_bytes": ([_i64, _i64, _i64, _i64], C.c_int64),

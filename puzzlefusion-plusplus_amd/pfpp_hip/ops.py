@@ -248,6 +248,23 @@ def _sync_attention_mode() -> None:
         _ATTN_MODE_SET.mode = want
 
 
+ATTN_CROSS_CHECK = {"DENSE_F32": 1, "BD_F32": 2, "BD_SCALAR": 4, "NO_SHORT": 8}      # csrc/attn_choice.h: ATTN_X_*
+
+
+@_ctx.contextmanager
+def attention_cross_check(*names: str):
+    """run the enclosed attention calls of this thread on the cross-check kernels `names` select (pfpp_set_attention_cross_check,
+    include/pfpp.h) instead of the default ones.  On exit the setting is what it was on entry: 0, the product's, outside any other
+    attention_cross_check, whose bits a nested one keeps.  For tests and measurements."""
+    lib = _lib.load()
+    prev = lib.pfpp_get_attention_cross_check()
+    check(lib.pfpp_set_attention_cross_check(prev | sum({ATTN_CROSS_CHECK[n] for n in names})), "pfpp_set_attention_cross_check")
+    try:
+        yield
+    finally:
+        check(lib.pfpp_set_attention_cross_check(prev), "pfpp_set_attention_cross_check")
+
+
 @_ctx.contextmanager
 def exact_fp32():
     """run the enclosed calls with the exact fp32 MFMA GEMMs (PFPP_GEMM=f32) — the fallback the drop-in sampler loops take

@@ -1,7 +1,6 @@
 """Case table, float64 reference and error report of the attention edge tests (no test in here; importable without a GPU).
 tests/test_attention_cases_host.py checks the table itself on the CPU, tests/test_gpu_attention_edges.py runs it through the HIP
-kernels, and `python tests/attention_cases.py` is the child process of the latter that runs the kernels behind the process-static
-PFPP_ATTN_* switches and prints one JSON line.
+kernels, once more per CROSS_CHECKS setting for the kernels that the defaults never pick.
 
 Both attentions read a packed projection qkv [rows, 3 H dh] = (q | k | v) and ragged groups (off, len) of rows: the sequences of the
 dense attention (csrc/attention.hip, attention_bwd.hip: 32-key tiles inside 128-row workgroups, optional key mask), the fragments
@@ -28,14 +27,10 @@ mask patterns that would empty a sequence run on the lengths they leave a key in
 key it keeps."""
 from __future__ import annotations
 
-import json
 import math
-import os
-import sys
 import zlib
 from dataclasses import dataclass, replace
 from functools import lru_cache
-from pathlib import Path
 from typing import Optional, Tuple
 
 import torch
@@ -135,8 +130,8 @@ F_CASES = ("A-dh64", "E_neg12-dh64")        # parts and planes: the split-f16 pa
 K_LS = (1, 17, 32)
 CHILD_DENSE = [n for n in DENSE if n[0] in "AC"]
 CHILD_BD = [n for n in BLOCKDIAG if n[0] == "I"]
-CHILD_ENVS = ({"PFPP_ATTN_F16X3": "0", "PFPP_ATTN_BD_F16X3": "0"},          # dense fp32 <64> unmasked, block-diagonal fp32 mfma
-              {"PFPP_ATTN_BD_F16X3": "0", "PFPP_ATTN_BD_MFMA": "0"})        # block-diagonal scalar kernel
+CROSS_CHECKS = (("DENSE_F32", "BD_F32"),          # ops.attention_cross_check names: dense fp32 <64> unmasked, block-diagonal fp32 mfma
+                ("BD_F32", "BD_SCALAR"))          # block-diagonal scalar kernels
 
 
 # ------------------------------------------------------------------------------------------------------------ inputs
@@ -378,17 +373,10 @@ def run_dense(c: Case, dev):
     out, lse = T.attn_dense_train(qkv, so, sl, c.T, H, dh, c.scale, key_valid=kv, out=filled(rows, C), lse=filled(rows, H))
     # the inference forward: as dispatched (launches of <= 64 workgroups at dh 64 go to attn_dense_short_kernel, which splits the keys
     # over the waves and so sums in another order: other bits by design, held to the bound of `out`), and with that kernel switched
-    # off for the call (PFPP_ATTN_SHORT_MAX is read per call), where it is the training forward's kernel and must give its bits
+    # off for the call (NO_SHORT, on top of what the caller has set), where it is the training forward's kernel and must give its bits
     fwd = ops.attn_dense(qkv, so, sl, c.T, H, dh, c.scale, kv, out=filled(rows, C))
-    prev = os.environ.get("PFPP_ATTN_SHORT_MAX")
-    os.environ["PFPP_ATTN_SHORT_MAX"] = "0"
-    try:
+    with ops.attention_cross_check("NO_SHORT"):
         walk = ops.attn_dense(qkv, so, sl, c.T, H, dh, c.scale, kv, out=filled(rows, C))
-    finally:
-        if prev is None:
-            del os.environ["PFPP_ATTN_SHORT_MAX"]
-        else:
-            os.environ["PFPP_ATTN_SHORT_MAX"] = prev
     dvec = filled(rows, H)
     dqkv = T.attn_dense_bwd(qkv, out, dout, lse, so, sl, c.T, H, dh, c.scale, key_valid=kv, out=filled(rows, 3 * C), dvec=dvec)
     torch.cuda.synchronize()
@@ -413,28 +401,3 @@ def run_blockdiag(c: Case, dev):
     dqkv = T.attn_blockdiag_bwd(qkv, dout, n_frag, L, c.H, c.dh, c.scale)
     torch.cuda.synchronize()
     return dict(out=out.cpu(), dqkv=dqkv.cpu()), dict(qkv=qkv, dout=dout, dqkv=dqkv)
-
-
-def child_main() -> int:
-    """run the A, C and I cases with whatever PFPP_ATTN_* switches this process was started under; one JSON line:
-    {case: {finite, ok, flags, worst}}"""
-    root = Path(__file__).resolve().parents[1]
-    sys.path[:0] = [str(root), str(root / "puzzlefusion-plusplus_amd")]
-    dev = torch.device("cuda:0")
-    res = {}
-    for name in CHILD_DENSE:
-        got, flags, _ = run_dense(DENSE[name], dev)
-        rep = report(DENSE[name], got)
-        print(describe(rep), file=sys.stderr)
-        res[name] = dict(finite=rep["finite"], ok=rep["ok"], flags=flags, worst=rep["worst"])
-    for name in CHILD_BD:
-        got, _ = run_blockdiag(BLOCKDIAG[name], dev)
-        rep = report(BLOCKDIAG[name], got)
-        print(describe(rep), file=sys.stderr)
-        res[name] = dict(finite=rep["finite"], ok=rep["ok"], flags={}, worst=rep["worst"])
-    print(json.dumps(res), flush=True)
-    return 0
-
-
-if __name__ == "__main__":
-    sys.exit(child_main())

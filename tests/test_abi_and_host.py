@@ -145,19 +145,28 @@ def test_library_built_without_the_correctness_switches_is_refused_at_load(monke
 
 
 def test_attention_mode_is_state_of_the_calling_thread(hip_lib):
-    """pfpp_set_attention_mode is thread-local (the library keeps no process-global mutable state): another host thread keeps the default"""
+    """pfpp_set_attention_mode and pfpp_set_attention_cross_check are thread-local (the library keeps no process-global mutable state):
+    another host thread keeps the defaults"""
     import threading
 
-    from pfpp_hip import _lib
+    from pfpp_hip import _lib, ops
 
     lib = _lib.load()
     assert lib.pfpp_set_attention_mode(0) == 0 and lib.pfpp_get_attention_mode() == 0
+    assert lib.pfpp_set_attention_cross_check(5) == 0 and lib.pfpp_get_attention_cross_check() == 5
     seen = []
-    th = threading.Thread(target=lambda: seen.append(lib.pfpp_get_attention_mode()))
+    th = threading.Thread(target=lambda: seen.append((lib.pfpp_get_attention_mode(), lib.pfpp_get_attention_cross_check())))
     th.start(); th.join()
-    assert seen == [-1]
+    assert seen == [(-1, 0)]
     assert lib.pfpp_set_attention_mode(-1) == 0 and lib.pfpp_get_attention_mode() == -1
     assert lib.pfpp_set_attention_mode(7) != 0
+    assert lib.pfpp_set_attention_cross_check(16) == -1 and lib.pfpp_get_attention_cross_check() == 5          # PFPP_EINVAL: an unknown bit
+    assert lib.pfpp_set_attention_cross_check(0) == 0
+    with ops.attention_cross_check("BD_F32"):
+        with ops.attention_cross_check("NO_SHORT"):
+            assert lib.pfpp_get_attention_cross_check() == 2 | 8
+        assert lib.pfpp_get_attention_cross_check() == 2
+    assert lib.pfpp_get_attention_cross_check() == 0
 
 
 def test_packing_geglu_and_sa_first():

@@ -9,9 +9,6 @@ dq / dk (D_g15-dh64, J_L7_g15, J_L32_g15: dS reaches 4.3 .. 6.5, past 65504 / 2^
 block maximum against the bound of 2e-5 (D_g1e-06-dh64, J_L32_g1e-06); now 8e-7 and 1.7e-5 / 1.1e-5.
 """
 import importlib.util
-import json
-import os
-import subprocess
 import sys
 from pathlib import Path
 
@@ -123,23 +120,27 @@ def test_blockdiag_backward_with_planes_is_the_same_bits(dev, L):
 
 
 # ------------------------------------------------------------------------------------------------------------ the switched-off kernels
-@pytest.mark.parametrize("env", ac.CHILD_ENVS, ids=lambda e: "+".join(f"{k[5:]}={v}" for k, v in e.items()))
-def test_kernels_behind_the_process_static_switches(dev, env):
+@pytest.mark.parametrize("names", ac.CROSS_CHECKS, ids="+".join)
+def test_kernels_behind_the_process_static_switches(dev, names):
     """The exact-fp32 kernels (attn_dense_bwd_*_kernel<64> unmasked, attn_blockdiag_bwd_mfma_kernel, attn_blockdiag_bwd_kernel and
-    the forward kernels the same switches select) are chosen by getenv once per process, so cases A, C and I run once more in a fresh
-    child process per setting (python tests/attention_cases.py: one JSON line of per-case worst blocks) and are held to the same
-    bounds, finiteness and bitwise properties."""
-    child_env = {k: v for k, v in os.environ.items() if not k.startswith("PFPP_ATTN_")}
-    child_env.update(env)
-    proc = subprocess.run([sys.executable, str(ROOT / "tests" / "attention_cases.py")], env=child_env, capture_output=True, text=True,
-                          timeout=120)
-    print(proc.stderr)
-    assert proc.returncode == 0, proc.stderr[-4000:]
-    res = json.loads(proc.stdout.strip().splitlines()[-1])
-    assert sorted(res) == sorted(ac.CHILD_DENSE + ac.CHILD_BD)
+    the forward kernels the same settings select) are never picked at the defaults (csrc/attn_choice.h), so cases A, C and I run once
+    more per cross-check setting (ops.attention_cross_check; once environment switches read once per process, hence the name) and are
+    held to the same bounds, finiteness and bitwise properties."""
+    from pfpp_hip import ops
+
     bad = {}
-    for name, r in res.items():
-        over = {qn: w for qn, w in r["worst"].items() if not w["err"] <= w["bound"]}
-        if not r["finite"] or over or not all(r["flags"].values()):
-            bad[name] = dict(finite=r["finite"], over=over, flags=r["flags"])
+    ops._sync_attention_mode()          # the default mode, whatever ran before: attn_dense_train does not put it back itself
+    with ops.attention_cross_check(*names):
+        for name in ac.CHILD_DENSE + ac.CHILD_BD:
+            if name in ac.DENSE:
+                c = ac.DENSE[name]
+                got, flags, _ = ac.run_dense(c, dev)
+            else:
+                c = ac.BLOCKDIAG[name]
+                (got, _), flags = ac.run_blockdiag(c, dev), {}
+            rep = ac.report(c, got)
+            print(ac.describe(rep))
+            over = {qn: w for qn, w in rep["worst"].items() if not w["err"] <= w["bound"]}
+            if not rep["finite"] or over or not all(flags.values()):
+                bad[name] = dict(finite=rep["finite"], over=over, flags=flags)
     assert not bad, bad

@@ -424,10 +424,10 @@ def test_attn_dense_fused_vs_float64_and_unfused(dev, B, T, H, dh):
 
 
 @pytest.mark.parametrize("lens,masked", [((25,), False), ((100,), False), ((250,), True), ((500,), False), ((333, 75), True), ((1,), False)])
-def test_attn_dense_short_sequences_keys_split_over_the_waves(dev, lens, masked, monkeypatch):
+def test_attn_dense_short_sequences_keys_split_over_the_waves(dev, lens, masked):
     """csrc/attention.hip attn_dense_short_kernel (one puzzle in flight: a few sequences of <= 512 tokens; 32-query workgroups whose
     four waves split the key tiles and merge their partial softmaxes in wave order) against float64, against the tile-walking kernel it
-    replaces there (PFPP_ATTN_SHORT_MAX=0) and twice (deterministic); fp32 output and plane output"""
+    replaces there (ops.attention_cross_check("NO_SHORT")) and twice (deterministic); fp32 output and plane output"""
     from pfpp_hip import ops
 
     H, dh = 8, 64
@@ -448,13 +448,12 @@ def test_attn_dense_short_sequences_keys_split_over_the_waves(dev, lens, masked,
     kv = None if valid is None else valid.to(torch.uint8).to(dev)
     scale = 1.0 / dh ** 0.5
     qd = qkv.to(dev)
-    monkeypatch.setenv("PFPP_ATTN_SHORT_MAX", "512")
     out = ops.attn_dense(qd, offs.to(dev), ln.to(dev), max_len, H, dh, scale, kv)
     out_b = ops.attn_dense(qd, offs.to(dev), ln.to(dev), max_len, H, dh, scale, kv)
     pl = ops.SplitAct.empty(rows, C, dev)
     ops.attn_dense(qd, offs.to(dev), ln.to(dev), max_len, H, dh, scale, kv, out=pl)
-    monkeypatch.setenv("PFPP_ATTN_SHORT_MAX", "0")
-    walk = ops.attn_dense(qd, offs.to(dev), ln.to(dev), max_len, H, dh, scale, kv)
+    with ops.attention_cross_check("NO_SHORT"):
+        walk = ops.attn_dense(qd, offs.to(dev), ln.to(dev), max_len, H, dh, scale, kv)
     assert torch.equal(out, out_b)
     assert (out - walk).abs().max() < 2e-6 * max(1.0, float(walk.abs().max()))
     assert (pl.float() - out).abs().max() < 1e-6 * max(1.0, float(out.abs().max()))
@@ -2244,3 +2243,140 @@ def test_sa_stage_kernel_choice_is_pinned(dev, case):
     call(dev)
     torch.cuda.synchronize()
     assert _lib.load().pfpp_last_gemm_kernel().decode() == want
+
+
+# ----------------------------------------------------------------------------- attention kernel choice
+# shapes of the dense cases: (sequence lengths, heads, dim_head)
+_ATTN_SHAPES = {
+    "len512": ((512,), 1, 64), "len513": ((513,), 1, 64),           # the short kernel's length limit, one workgroup row of queries
+    "wg64": ((16,) * 8, 8, 64), "wg65": ((16,) * 5, 13, 64),        # ... and its limit of 64 tile-walker workgroups
+    "one16": ((16,), 1, 64), "dh32_16": ((16,), 1, 32),
+    "dh32_1023": ((1023,), 1, 32), "dh32_1024": ((1024,), 1, 32),   # dim_head 32: split-f16 from 1,024 keys on
+}
+_ATTN_BD = (2, 4, 2)            # block-diagonal cases: 2 fragments of 4 rows, 2 heads
+
+
+def _attn_choice_cases():
+    """name -> (kind, shape, masked (dense) or plane output (block-diagonal), attention mode, cross-check names, expected
+    pfpp_last_gemm_kernel()).  kind: fwd = pfpp_attn_dense, train = pfpp_attn_dense_train, bwd = pfpp_attn_dense_bwd, bwd_p =
+    pfpp_attn_dense_bwd_p with plane output only, parts = pfpp_attn_dense_bwd_parts with bits 7, bd_fwd = pfpp_attn_blockdiag,
+    bd_bwd = pfpp_attn_blockdiag_bwd / _p.  "" = the call is refused (PFPP_EUNSUPPORTED) and launches nothing.  The names are a
+    transcription of profiles/attn_choice_parent_per_case.txt."""
+    short, walk, walk32, single, single32 = ("attn_dense_short_kernel<64>", "attn_dense_f16_kernel<64, false>", "attn_dense_f16_kernel<32, false>",
+                                             "attn_dense_f16_kernel<64, true>", "attn_dense_f16_kernel<32, true>")
+    f32, f32_32 = "attn_dense_kernel<64>", "attn_dense_kernel<32>"
+    b16 = "attn_dense_bwd_dq_f16_kernel+attn_dense_bwd_dkv_f16_kernel"
+    b64 = "attn_dense_bwd_dq_kernel<64>+attn_dense_bwd_dkv_kernel<64>"
+    b32 = "attn_dense_bwd_dq_kernel<32>+attn_dense_bwd_dkv_kernel<32>"
+    d64, d32 = "attn_dense_bwd_d_kernel<64>+", "attn_dense_bwd_d_kernel<32>+"
+    bd16, bdm, bds = "attn_blockdiag_f16_kernel", "attn_blockdiag_mfma_kernel", "attn_blockdiag_kernel"
+    gb16, gbm, gbs = "attn_blockdiag_bwd_f16_kernel", "attn_blockdiag_bwd_mfma_kernel", "attn_blockdiag_bwd_kernel"
+    NS, DF, BF, BS = ("NO_SHORT",), ("DENSE_F32",), ("BD_F32",), ("BD_SCALAR",)
+    BD = _ATTN_BD
+    table = [
+        # ---- dense forward: both sides of every edge at the defaults, inference against training at a short shape
+        ("fwd_len512", "fwd", "len512", False, -1, (), short), ("fwd_len513", "fwd", "len513", False, -1, (), walk),
+        ("fwd_wg64", "fwd", "wg64", False, -1, (), short), ("fwd_wg65", "fwd", "wg65", False, -1, (), walk),
+        ("fwd_dh32_1023", "fwd", "dh32_1023", False, -1, (), f32_32), ("fwd_dh32_1024", "fwd", "dh32_1024", False, -1, (), walk32),
+        ("fwd_one16", "fwd", "one16", False, -1, (), short), ("train_one16", "train", "one16", False, -1, (), walk),
+        # ---- every rule under modes 0 and 2, NO_SHORT and DENSE_F32
+        ("fwd_one16_mode0", "fwd", "one16", False, 0, (), f32), ("fwd_one16_mode2", "fwd", "one16", False, 2, (), single),
+        ("fwd_one16_no_short", "fwd", "one16", False, -1, NS, walk), ("fwd_one16_dense_f32", "fwd", "one16", False, -1, DF, f32),
+        ("fwd_len513_mode0", "fwd", "len513", False, 0, (), f32), ("fwd_len513_mode2", "fwd", "len513", False, 2, (), single),
+        ("fwd_len513_no_short", "fwd", "len513", False, -1, NS, walk), ("fwd_len513_dense_f32", "fwd", "len513", False, -1, DF, f32),
+        ("fwd_dh32_1024_mode0", "fwd", "dh32_1024", False, 0, (), f32_32), ("fwd_dh32_1024_mode2", "fwd", "dh32_1024", False, 2, (), single32),
+        ("fwd_dh32_1024_no_short", "fwd", "dh32_1024", False, -1, NS, walk32), ("fwd_dh32_1024_dense_f32", "fwd", "dh32_1024", False, -1, DF, f32_32),
+        ("fwd_dh32_1023_mode0", "fwd", "dh32_1023", False, 0, (), f32_32), ("fwd_dh32_1023_mode2", "fwd", "dh32_1023", False, 2, (), single32),
+        ("fwd_dh32_1023_no_short", "fwd", "dh32_1023", False, -1, NS, f32_32), ("fwd_dh32_1023_dense_f32", "fwd", "dh32_1023", False, -1, DF, f32_32),
+        ("train_one16_mode2", "train", "one16", False, 2, (), walk), ("train_one16_mode0", "train", "one16", False, 0, (), f32),
+        ("fwd_one16_mode2_dense_f32", "fwd", "one16", False, 2, DF, single), ("fwd_len513_mode1_dense_f32", "fwd", "len513", False, 1, DF, walk),
+        ("train_one16_mode1_dense_f32", "train", "one16", False, 1, DF, walk), ("train_one16_dense_f32", "train", "one16", False, -1, DF, f32),
+        # ---- dense backward: the mode is not consulted; planes only from the split-f16 passes
+        ("bwd_unmasked", "bwd", "one16", False, -1, (), b16), ("bwd_masked", "bwd", "one16", True, -1, (), b64),
+        ("bwd_dh32", "bwd", "dh32_16", False, -1, (), b32), ("bwd_dense_f32", "bwd", "one16", False, -1, DF, b64),
+        ("bwd_mode0", "bwd", "one16", False, 0, (), b16),
+        ("bwd_p_unmasked", "bwd_p", "one16", False, -1, (), b16), ("bwd_p_masked", "bwd_p", "one16", True, -1, (), ""),
+        ("bwd_p_dh32", "bwd_p", "dh32_16", False, -1, (), ""), ("bwd_p_dense_f32", "bwd_p", "one16", False, -1, DF, ""),
+        ("bwd_p_mode0", "bwd_p", "one16", False, 0, (), b16),
+        ("parts_unmasked", "parts", "one16", False, -1, (), d64 + b16), ("parts_masked", "parts", "one16", True, -1, (), d64 + b64),
+        ("parts_dh32", "parts", "dh32_16", False, -1, (), d32 + b32), ("parts_dense_f32", "parts", "one16", False, -1, DF, d64 + b64),
+        ("parts_mode0", "parts", "one16", False, 0, (), d64 + b16),
+        # ---- block-diagonal forward
+        ("bd_fwd_mode-1", "bd_fwd", BD, False, -1, (), bd16), ("bd_fwd_mode-1_bd_f32", "bd_fwd", BD, False, -1, BF, bdm),
+        ("bd_fwd_mode0", "bd_fwd", BD, False, 0, (), bdm), ("bd_fwd_mode0_bd_f32", "bd_fwd", BD, False, 0, BF, bdm),
+        ("bd_fwd_mode1", "bd_fwd", BD, False, 1, (), bd16), ("bd_fwd_mode1_bd_f32", "bd_fwd", BD, False, 1, BF, bd16),
+        ("bd_fwd_mode2", "bd_fwd", BD, False, 2, (), bd16), ("bd_fwd_mode2_bd_f32", "bd_fwd", BD, False, 2, BF, bd16),
+        ("bd_fwd_bd_scalar", "bd_fwd", BD, False, -1, BS, bds), ("bd_fwd_bd_scalar_mode0", "bd_fwd", BD, False, 0, BS, bds),
+        ("bd_fwd_both", "bd_fwd", BD, False, -1, BF + BS, bds),
+        # ---- block-diagonal backward: the mode is not consulted; a call with planes keeps a matrix-instruction kernel
+        ("bd_bwd", "bd_bwd", BD, False, -1, (), gb16), ("bd_bwd_mode0", "bd_bwd", BD, False, 0, (), gb16),
+        ("bd_bwd_bd_f32", "bd_bwd", BD, False, -1, BF, gbm), ("bd_bwd_bd_scalar", "bd_bwd", BD, False, -1, BS, gbs),
+        ("bd_bwd_both", "bd_bwd", BD, False, -1, BF + BS, gbs),
+        ("bd_bwd_planes", "bd_bwd", BD, True, -1, (), gb16), ("bd_bwd_planes_mode0", "bd_bwd", BD, True, 0, (), gb16),
+        ("bd_bwd_planes_bd_f32", "bd_bwd", BD, True, -1, BF, gbm), ("bd_bwd_planes_bd_scalar", "bd_bwd", BD, True, -1, BS, gb16),
+        ("bd_bwd_planes_both", "bd_bwd", BD, True, -1, BF + BS, gbm),
+    ]
+    return {row[0]: row[1:] for row in table}
+
+
+def _attn_choice_call(lib, dev, kind, shape, flag):
+    """one library call on random inputs of the smallest valid size -> its return code"""
+    from pfpp_hip import ops, planes as P
+
+    ptr, st = ops._ptr, ops._stream
+    g = torch.Generator().manual_seed(5)
+    if kind.startswith("bd_"):
+        n_frag, L, H = shape
+        dh, C = 64, H * 64
+        qkv = torch.randn(n_frag * L, 3 * C, generator=g).to(dev)
+        if kind == "bd_fwd":
+            return lib.pfpp_attn_blockdiag(ptr(qkv), ptr(torch.empty(n_frag * L, C, device=dev)), n_frag, L, H, dh, 0.125, st())
+        dout = torch.randn(n_frag * L, C, generator=g).to(dev)
+        if flag:
+            dq = P.Planes.empty(qkv.shape[0], 3 * C, dev, 4096.0)
+            return lib.pfpp_attn_blockdiag_bwd_p(ptr(qkv), ptr(dout), None, n_frag, L, H, dh, 0.125, P._pl(dq), st())
+        return lib.pfpp_attn_blockdiag_bwd(ptr(qkv), ptr(dout), ptr(torch.empty_like(qkv)), n_frag, L, H, dh, 0.125, st())
+    lens, H, dh = _ATTN_SHAPES[shape]
+    rows, n_seq, T, C = sum(lens), len(lens), max(lens), H * dh
+    scale = dh ** -0.5
+    qkv = torch.randn(rows, 3 * C, generator=g).to(dev)
+    so = torch.tensor([sum(lens[:i]) for i in range(n_seq)], dtype=torch.int32, device=dev)
+    sl = torch.tensor(lens, dtype=torch.int32, device=dev)
+    kv = torch.ones(n_seq, T, dtype=torch.uint8, device=dev) if flag else None
+    tail = (ptr(so), ptr(sl), ptr(kv), T if flag else 0, n_seq, T, H, dh, scale)
+    out, lse = torch.zeros(rows, C, device=dev), torch.full((rows, H), 8.0, device=dev)
+    if kind == "fwd":
+        return lib.pfpp_attn_dense(ptr(qkv), ptr(out), *tail, st())
+    if kind == "train":
+        return lib.pfpp_attn_dense_train(ptr(qkv), ptr(out), ptr(lse), *tail, st())
+    dout = torch.randn(rows, C, generator=g).to(dev)
+    dvec, dqkv = torch.zeros(rows, H, device=dev), torch.zeros(rows, 3 * C, device=dev)
+    if kind == "bwd":
+        return lib.pfpp_attn_dense_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dvec), ptr(dqkv), *tail, st())
+    if kind == "parts":
+        return lib.pfpp_attn_dense_bwd_parts(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dvec), ptr(dqkv), *tail, 7, st())
+    dq = P.Planes.empty(rows, 3 * C, dev, 4096.0)
+    return lib.pfpp_attn_dense_bwd_p(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dvec), None, *tail, P._pl(dq), st())
+
+
+@pytest.mark.parametrize("case", list(_attn_choice_cases()))
+def test_attention_kernel_choice_is_pinned(dev, case):
+    """Every attention entry point picks its kernel(s) by a pure function of the call's sizes and flags, the calling thread's attention
+    mode and its cross-check bits (csrc/attn_choice.h); this pins the pick at both sides of every edge of those rules, one call per
+    case.  The expected names are what a kernel trace of this case list printed at the commit before the choice became those
+    functions, when environment switches stood where the bits do (profiles/attn_choice_parent_per_case.txt: one process per setting
+    under rocprofv3 --kernel-trace; the names with a _Float16 parameter demangled), several launches of one call joined with '+'."""
+    from pfpp_hip import _lib, ops
+
+    kind, shape, flag, mode, cross, want = _attn_choice_cases()[case]
+    lib = _lib.load()
+    assert lib.pfpp_set_attention_mode(mode) == 0          # set through the library: the wrappers of ops would put their own back
+    try:
+        with ops.attention_cross_check(*cross):
+            rc = _attn_choice_call(lib, dev, kind, shape, flag)
+            torch.cuda.synchronize()
+    finally:
+        assert lib.pfpp_set_attention_mode(-1) == 0
+        ops._ATTN_MODE_SET.mode = -1
+    assert rc == (0 if want else -2), lib.pfpp_last_error().decode()
+    assert lib.pfpp_last_gemm_kernel().decode() == want
