@@ -1432,6 +1432,47 @@ int pfpp_ptf_train_bwd_gather(const float* dout, const float* w, const float* du
                               const float* pack, int64_t N, int64_t C, int64_t K, const int64_t* off_k, const int32_t* ent_k,
                               const int64_t* off_v, const int32_t* ent_v, float* dqkv, int64_t ldg, pfpp_stream_t stream);
 
+/* ---- matcher front end, training: the ragged PointNet++ encoder in .train() under autograd (pointnet2_pointwise/pointnet2_msg.py:48-94,
+ * pointnet2_dynamic_utils.py; csrc/pointnet_ragged_train.hip) around the exact-fp32 GEMMs.  Sampling, search, grouping and interpolation
+ * are the forward's entries.  Each of the 33 convolutions in front of conv1 is followed by a BatchNorm on the statistics of ALL rows of the call and a ReLU
+ * (pointnet2_dynamic_utils.py:147-150 BatchNorm2d over [1, C, K, S]; :220-222 BatchNorm1d over [1, C, N]).  C % 4 == 0, C <= 1024; rows of
+ * ld floats, ld % 4 == 0, 16-byte aligned.  workspace: PFPP_RAGGED_TRAIN_WS_DOUBLES doubles whatever the sizes are.  No atomics: two runs
+ * agree bitwise.
+ * pfpp_ragged_bn_stats (nn.BatchNorm2d / 1d in .train(), :150 and :222): sums of y and y^2 per channel over the rows, one fp64 partial per
+ *   workgroup (a workgroup takes ceil(rows / G) consecutive rows, G = min(PFPP_RAGGED_TRAIN_MAX_WG, ceil(rows / 64))), folded in a fixed
+ *   order; coef [4 C] = a | b | mean | rstd with rstd = 1 / sqrt(var + eps) (biased variance), a = gamma rstd, b = beta - mean a;
+ *   running_mean / running_var (optional, together) move by `momentum` with the unbiased variance, in fp64, rounded once (eps and
+ *   momentum are doubles, as in torch).  rows >= 2.
+ * pfpp_ragged_bn_apply (:150 F.relu(bn(conv)) and the max over the K rows of a neighbourhood :151): out [rows, ldo] = max(fma(y, a, b), 0);
+ *   with pool > 0 out [rows / pool, ldo] = the max over each `pool` consecutive rows and winner int32 [rows / pool, C] (optional) = the first
+ *   row of the group that attains it, -1 when every row is <= 0.
+ * pfpp_ragged_pool_bwd (autograd of torch.max(., 2)[0] :151): dh [groups pool, C] = dout[g, c] (row stride ldd) on the winning row as
+ *   pfpp_ragged_bn_apply finds it, 0 elsewhere.
+ * pfpp_ragged_bn_relu_bwd (autograd of :150 / :222): dz = dh where fma(y, a, b) > 0 — the forward's expression, bit for bit — else 0;
+ *   dbeta = sum dz and dgamma = sum dz xhat (fp64 sums, OVERWRITTEN), xhat = (y - mean) rstd; dy [rows, C] = gamma rstd ((dz - mean dz) -
+ *   xhat mean(dz xhat)).  dh is [rows, C] contiguous; dy may alias dh.
+ * pfpp_ragged_group_bwd (autograd of the gathers :138-142): dfeats[p, 0:D] (=, or += with accumulate) sum over the entries e of
+ *   ent[off[p] .. off[p + 1]) in that order of dA[(e / K) pool + e % K, 0:D]; e = s K + j names slot j of centroid s (idx [S, K] flat),
+ *   off int64 [Np + 1], ent int32 [S K] ascending per point.  A point in no list gets zeros (or keeps its value).  The coordinate columns
+ *   D .. D + 2 of dA are not read: the coordinates are inputs.
+ * pfpp_ragged_interp_bwd (autograd of :208-211): dpoints2[s, 0:D2] = sum over the entries e = 3 i + j of ent[off[s] .. off[s + 1]) of
+ *   weights[e] dout[i, D1 : D1 + D2] (padded slots included: they carry the first index and the weight 1e8 gives); S == 1 (:191-192, the
+ *   broadcast; weights / off / ent unused): dpoints2[0] = the column sums over all N rows, fp64 partials folded in a fixed order.     */
+#define PFPP_RAGGED_TRAIN_MAX_WG 256
+#define PFPP_RAGGED_TRAIN_WS_DOUBLES (PFPP_RAGGED_TRAIN_MAX_WG * 2 * 1024 + 1024)
+int pfpp_ragged_bn_stats(const float* y, int64_t rows, int64_t C, int64_t ld, const float* gamma, const float* beta, double eps, double momentum,
+                         float* running_mean, float* running_var, float* coef, double* workspace, pfpp_stream_t stream);
+int pfpp_ragged_bn_apply(const float* y, int64_t rows, int64_t C, int64_t ld, const float* coef, float* out, int64_t ldo, int64_t pool,
+                         int32_t* winner, pfpp_stream_t stream);
+int pfpp_ragged_pool_bwd(const float* y, int64_t groups, int64_t pool, int64_t C, int64_t ld, const float* coef, const float* dout, int64_t ldd,
+                         float* dh, pfpp_stream_t stream);
+int pfpp_ragged_bn_relu_bwd(const float* y, const float* dh, int64_t rows, int64_t C, int64_t ld, const float* coef, const float* gamma,
+                            float* dgamma, float* dbeta, float* dy, double* workspace, pfpp_stream_t stream);
+int pfpp_ragged_group_bwd(const float* dA, int64_t lda, int64_t D, const int64_t* off, const int32_t* ent, int64_t S, int64_t K, int64_t pool,
+                          int64_t Np, float* dfeats, int64_t ldf, int accumulate, pfpp_stream_t stream);
+int pfpp_ragged_interp_bwd(const float* dout, int64_t ldo, int64_t D1, int64_t D2, const float* weights, const int64_t* off, const int32_t* ent,
+                           int64_t N, int64_t S, float* dpoints2, double* workspace, pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

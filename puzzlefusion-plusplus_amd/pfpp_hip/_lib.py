@@ -369,6 +369,12 @@ SIGNATURES = {
     "pfpp_ptf_train_bwd_u": [_p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p],
     "pfpp_ptf_train_bwd_r": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p],
     "pfpp_ptf_train_bwd_gather": [_p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p],
+    "pfpp_ragged_bn_stats": [_p, _i64, _i64, _i64, _p, _p, C.c_double, C.c_double, _p, _p, _p, _p, _p],
+    "pfpp_ragged_bn_apply": [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p],
+    "pfpp_ragged_pool_bwd": [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p],
+    "pfpp_ragged_bn_relu_bwd": [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p],
+    "pfpp_ragged_group_bwd": [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, C.c_int, _p],
+    "pfpp_ragged_interp_bwd": [_p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
