@@ -1345,6 +1345,54 @@ int pfpp_match_gather_raw(const float* feats, const int64_t* idx, int64_t N, int
 int pfpp_match_scatter_raw(const float* in, const int64_t* idx, int64_t N, int64_t R, int64_t C, int accumulate, float* out,
                            pfpp_stream_t stream);
 
+/* ---- matcher head, training: the rigid term (Jigsaw_matching/utils/loss.py:59-142 with utils/pairwise_alignment.py:11-79, called at
+ * model/jigsaw/joint_seg_align_model.py:379-392 once w_rig_loss > 0; csrc/matching_rigid.hip, the seeded backward in
+ * csrc/matching_train.hip).  The reference loops over the piece pairs of every puzzle in Python and solves Horn's 4 x 4 eigenproblem
+ * per pair in numpy on the host; here the term and its gradient are four kernels and nothing is read back.
+ * A puzzle's n critical rows are in piece order: piece_off int32 [P + 1] (puzzle-local, piece_off[P] = n, P <= 64) are the pieces'
+ * first rows; pts float32 [n, 3] = the critical points taken from part_pcs in row order.  For a pair p < q with n1, n2 > 0 rows:
+ * W = ds_mat[I_p, I_q] + ds_mat[I_q, I_p]^T, r_i = sum_j W_ij, b_i = sum_j W_ij T_j (S = pts[I_p], T = pts[I_q]), mat_s = sum_i r_i.
+ * pfpp_rigid_pair_sums (loss.py:89-97, :124-127): one pass over ds_mat [n, n] (row stride ld): rb fp64 [n, P, 4] receives (r_i, b_i) of
+ * every row i against every LATER piece q; the other slots are not written.  The transposed half is read along its rows and
+ * transposed through LDS.  any_pos int32 [1] (zeroed by the caller) is set when an entry of ds_mat is positive (:75, :98).
+ * pfpp_rigid_pair_pose (pairwise_alignment.py:11-79, loss.py:109-135): all pairs of a batch in one launch, a wave per pair.  pairs int32
+ * [npairs, 4] = (puzzle, p, q, unused) in pair order; puz_row_off int64 [B + 1] = the puzzles' first rows in the batch-wide pts [R, 3]
+ * and rb [R, P, 4]; piece_off int32 [B, P + 1]; n_valid int32 [B]; any_pos int32 [B].  Unweighted centroids, M = sum_i (S_i - cS)
+ * (b_i - r_i cT)^T, Horn's N, a cyclic Jacobi of ten sweeps from the identity in fp64, the eigenvector of the FIRST of the largest
+ * eigenvalues (N = 0 gives R = 1, as LAPACK does for the reference), t = sum_i (b_i - r_i R S_i) / mat_s; R [npairs, 9] and t
+ * [npairs, 3] are rounded to fp32 and constant from here on.  stats fp64 [npairs, 8] = (mat_s, pair_loss = sum_i |r_i (R S_i + t) -
+ * b_i|^2, the four eigenvalues ascending, n1, n2); status int32 [npairs]: 1 kept, 0 skipped (:98: n_valid > 2, mat_s == 0 and a
+ * positive entry), -1 where the reference divides 0 by 0 (mat_s == 0 otherwise; pair_loss and t are stored as 0).
+ * pfpp_rigid_fold (:134-135, :142): out fp64 [4] = (rig_loss = sum pair_loss mat_s / n_sum over the kept pairs, in pair order;
+ * w_rig_loss / n_sum; n_sum = sum n1; the numerator).  Where the reference is not finite - a status of -1 anywhere, or nothing kept -
+ * rig_loss and the scale are 0: the term is reported as 0 and has zero gradient.  npairs = 0 is that case, not an error.
+ * pfpp_rigid_grad (autograd of :120-135 with R, t constant): dP [n, n] (row stride ldg) = d(w_rig_loss rig_loss) / d ds_mat of one
+ * puzzle: with a the row in the earlier piece and c the row in the later one, out[1] (2 mat_s e_a . (A_a - T_c) + pair_loss), the
+ * same for [a, c] and [c, a]; exact zeros in diagonal blocks and in pairs not kept.  pair_index int32 [P, P]: the pair of (p, q), p <
+ * q, or -1.  pts, piece_off, rb are the puzzle's own (offset by its first row); R, t, stats, status the batch's; fold = out above.
+ * All sums fp64 in a fixed order, no float atomics: two runs agree bitwise.  n = 0 and npairs = 0 launch nothing.
+ * pfpp_sinkhorn_train_bwd_seeded: pfpp_sinkhorn_train_bwd with ds holding a further term's dLoss' / d ds_mat on entry (zero padding
+ * columns included): G_T = the BCE term + P * seed, then the same max_iter passes; a zero seed gives pfpp_sinkhorn_train_bwd's result.
+ * pfpp_match_colsum_ordered: out[c] = sum_r x[r, c] over x [rows, cols] (row stride ld), OVERWRITTEN: fp64 partials of 64 rows in row
+ * order, folded in block order, rounded once.  The head's two bias gradients: pfpp_colsum ends in float atomics whose order differs
+ * from run to run, and the step is compared bitwise between runs.  workspace: pfpp_match_colsum_ordered_workspace(rows, cols) bytes
+ * (-1 for rows < 0 or cols < 1); rows = 0 writes zeros.                                                                           */
+int pfpp_rigid_pair_sums(const float* ds_mat, int64_t ld, int64_t n, const float* pts, const int32_t* piece_off, int64_t P, double* rb,
+                         int32_t* any_pos, pfpp_stream_t stream);
+int pfpp_rigid_pair_pose(int64_t npairs, const int32_t* pairs, const int64_t* puz_row_off, const int32_t* piece_off, int64_t P,
+                         const int32_t* n_valid, const int32_t* any_pos, const double* rb, const float* pts, float* R, float* t,
+                         double* stats, int32_t* status, pfpp_stream_t stream);
+int pfpp_rigid_fold(int64_t npairs, const double* stats, const int32_t* status, double w_rig_loss, double* out, pfpp_stream_t stream);
+int pfpp_rigid_grad(int64_t n, const float* pts, const int32_t* piece_off, int64_t P, const double* rb, const int32_t* pair_index,
+                    const float* R, const float* t, const double* stats, const int32_t* status, const double* fold, float* dP,
+                    int64_t ldg, pfpp_stream_t stream);
+int pfpp_sinkhorn_train_bwd_seeded(const float* s, int64_t ld, int64_t n, float tau, int64_t max_iter, const int32_t* tgt,
+                                   const double* pots, const float* ds_mat, float g, float* ds, int64_t ldg, void* workspace,
+                                   int64_t workspace_bytes, pfpp_stream_t stream);
+int64_t pfpp_match_colsum_ordered_workspace(int64_t rows, int64_t cols);
+int pfpp_match_colsum_ordered(const float* x, int64_t ld, int64_t rows, int64_t cols, float* out, void* workspace, int64_t workspace_bytes,
+                              pfpp_stream_t stream);
+
 /* ---- matcher middle, training: the backward of the cross-attention layer tf_cross1 (Jigsaw_matching/model/jigsaw/attention_layer.py in
  * .train() under autograd; csrc/matching_tf_train.hip).  The layer has no dropout (:15, :44, :86, :92 are commented out) and its
  * norms are nn.LayerNorm: its training-time forward is the eval forward.  The linear layers' gradients go through pfpp_gemm in its

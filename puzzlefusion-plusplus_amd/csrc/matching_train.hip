@@ -14,9 +14,11 @@
 //    skt_bwd_cols_kernel (a thread per column over 64-row blocks) its ordered column partials — each step is run in the layout
 //    whose sums the NEXT step (the other direction) needs, so a step costs one read of s and one read-modify-write of G.  The first
 //    pass (INIT) writes G_T = (P - y) P / max(P (1 - P), 1e-12) g, PyTorch's binary_cross_entropy backward times P, in the
-//    layout step T - 1 needs.  No float atomics anywhere: two runs agree bitwise.
+//    layout step T - 1 needs.  No float atomics anywhere: two runs agree bitwise.  SEED (pfpp_sinkhorn_train_bwd_seeded): the
+//    matrix holds dLoss' / d ds_mat of a further term on entry (the rigid term, matching_rigid.hip) and the first pass adds P * seed.
 //  * match_gt_targets_kernel — the target column of every critical row: nearest critical point of another piece of the puzzle.
 //  * match_normalize_halves_bwd_kernel, match_cls_bce_kernel (+ its fold), raw gather / scatter-add of the critical rows.
+//  * match_colsum_part_kernel + match_colsum_fold_kernel — the bias gradients' column sums in a fixed order.
 #include "pfpp_common.h"
 #include "sinkhorn_common.h"
 
@@ -179,8 +181,9 @@ __device__ __forceinline__ float skt_g_init(float p, bool y, float g) {
 __device__ __forceinline__ float skt_g_update(float gv, float p, double sum) { return (float)((double)gv - (double)p * sum); }
 
 // a wave per row.  INIT: G = G_T from P = ds_mat; else the column step G -= P_i * cs[j].  Leaves rs[i] = the row sum of the new G.
-// div: tau in the last pass (ds = G_0 / tau), 1 before.
-template <bool INIT>
+// div: tau in the last pass (ds = G_0 / tau), 1 before.  SEED (with INIT): G holds dLoss' / dP of another term on entry and the pass
+// writes G_T + P * seed (pfpp_sinkhorn_train_bwd_seeded).
+template <bool INIT, bool SEED = false>
 __global__ __launch_bounds__(256) void skt_bwd_rows_kernel(const float* __restrict__ s, int64_t ld, int n, float tau,
                                                            const double* __restrict__ u, const double* __restrict__ v,
                                                            const float* __restrict__ P, const int32_t* __restrict__ tgt, float g,
@@ -203,6 +206,7 @@ __global__ __launch_bounds__(256) void skt_bwd_rows_kernel(const float* __restri
       const int jc = j < n ? j : n - 1;
       a[k] = row[jc];
       if (!INIT) { gv[k] = grow[jc]; vj[k] = v ? v[jc] : 0.0; cj[k] = cs[jc]; }
+      if (SEED) gv[k] = grow[jc];
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -211,6 +215,7 @@ __global__ __launch_bounds__(256) void skt_bwd_rows_kernel(const float* __restri
         float gn;
         if (INIT) gn = skt_g_init(a[k], j == t, g);
         else gn = skt_g_update(gv[k], expf(sk_entry(a[k], tau, ui, vj[k])), cj[k]);
+        if (SEED) gn = gn + a[k] * gv[k];
         gn = gn / div;
         grow[j] = gn;
         acc += (double)gn;
@@ -223,7 +228,7 @@ __global__ __launch_bounds__(256) void skt_bwd_rows_kernel(const float* __restri
 
 // a thread per column over a block of 64 rows.  INIT as above; else the row step G -= P_i * rs[i].  Leaves cp[block, j] = the
 // column sum of the new G over the block's rows, in row order.
-template <bool INIT>
+template <bool INIT, bool SEED = false>
 __global__ __launch_bounds__(256) void skt_bwd_cols_kernel(const float* __restrict__ s, int64_t ld, int n, float tau,
                                                            const double* __restrict__ u, const double* __restrict__ v,
                                                            const float* __restrict__ P, const int32_t* __restrict__ tgt, float g,
@@ -252,7 +257,7 @@ __global__ __launch_bounds__(256) void skt_bwd_cols_kernel(const float* __restri
     for (int k = 0; k < 4; ++k) {
       const int r = min(r0 + k, rows - 1);
       a[k] = col[(int64_t)r * lds_];
-      if (!INIT) gv[k] = gcol[(int64_t)r * ldg];
+      if (!INIT || SEED) gv[k] = gcol[(int64_t)r * ldg];
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -261,6 +266,7 @@ __global__ __launch_bounds__(256) void skt_bwd_cols_kernel(const float* __restri
         float gn;
         if (INIT) gn = skt_g_init(a[k], j == st[r], g);
         else gn = skt_g_update(gv[k], expf(sk_entry(a[k], tau, su[r], vj)), srs[r]);
+        if (SEED) gn = gn + a[k] * gv[k];
         gn = gn / div;
         gcol[(int64_t)r * ldg] = gn;
         acc += (double)gn;
@@ -438,6 +444,29 @@ __global__ __launch_bounds__(256) void match_scatter_raw_kernel(const float* __r
   *dst = x;
 }
 
+// ------------------------------------------------------------------------------------------------ ordered column sums
+// the bias gradients: part[block, c] = sum of x[r, c] over the block's 64 rows in row order (fp64), then the blocks in block order.
+// pfpp_colsum ends in float atomics, whose order differs from run to run; here two runs agree bitwise.
+constexpr int OC_ROWS = 64;
+
+__global__ __launch_bounds__(256) void match_colsum_part_kernel(const float* __restrict__ x, int64_t ld, int64_t rows, int cols,
+                                                                double* __restrict__ part) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cols) return;
+  const int64_t r0 = (int64_t)blockIdx.y * OC_ROWS, r1 = min(rows, r0 + OC_ROWS);
+  double acc = 0.0;
+  for (int64_t r = r0; r < r1; ++r) acc += (double)x[r * ld + c];
+  part[(int64_t)blockIdx.y * cols + c] = acc;
+}
+
+__global__ __launch_bounds__(256) void match_colsum_fold_kernel(const double* __restrict__ part, int64_t nblk, int cols, float* __restrict__ out) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cols) return;
+  double acc = 0.0;
+  for (int64_t b = 0; b < nblk; ++b) acc += part[b * cols + c];
+  out[c] = (float)acc;
+}
+
 // workspace of the training Sinkhorn: column partials (fp64 sums, fp32 maxima) and two fp64 vectors (row sums / row losses, column sums)
 struct SktWs {
   double* ps;
@@ -492,14 +521,23 @@ extern "C" int pfpp_sinkhorn_train_fwd(const float* s, int64_t ld, int64_t n, fl
   return pfpp::check_launch(__func__);
 }
 
-extern "C" int pfpp_sinkhorn_train_bwd(const float* s, int64_t ld, int64_t n, float tau, int64_t max_iter, const int32_t* tgt,
-                                       const double* pots, const float* ds_mat, float g, float* ds, int64_t ldg, void* workspace,
-                                       int64_t workspace_bytes, pfpp_stream_t stream) {
-  PFPP_REQUIRE(s && tgt && ds_mat && ds && (pots || max_iter == 0), "null pointer");
-  PFPP_REQUIRE(n >= 1 && ld >= n && ldg >= n && max_iter >= 0 && tau > 0.0f, "bad sizes");
-  PFPP_SUPPORTED(n <= 65535, "more than 65535 critical points in one puzzle");
-  PFPP_REQUIRE(workspace && workspace_bytes >= pfpp_sinkhorn_train_workspace(n), "workspace smaller than pfpp_sinkhorn_train_workspace(n)");
-  PFPP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "workspace must be 8-byte aligned");
+namespace {
+// both backward entries: SEED = ds holds a further term's dLoss' / d ds_mat on entry.  The checks report under the entry's name.
+template <bool SEED>
+int skt_bwd_run(const char* func, const float* s, int64_t ld, int64_t n, float tau, int64_t max_iter, const int32_t* tgt, const double* pots,
+                const float* ds_mat, float g, float* ds, int64_t ldg, void* workspace, int64_t workspace_bytes, pfpp_stream_t stream) {
+  const char* bad = nullptr;
+  if (!(s && tgt && ds_mat && ds && (pots || max_iter == 0))) bad = "null pointer";
+  else if (!(n >= 1 && ld >= n && ldg >= n && max_iter >= 0 && tau > 0.0f)) bad = "bad sizes";
+  else if (n > 65535) {
+    pfpp::set_error("%s: unsupported: %s", func, "more than 65535 critical points in one puzzle");
+    return PFPP_EUNSUPPORTED;
+  } else if (!(workspace && workspace_bytes >= pfpp_sinkhorn_train_workspace(n))) bad = "workspace smaller than pfpp_sinkhorn_train_workspace(n)";
+  else if ((reinterpret_cast<uintptr_t>(workspace) & 7u) != 0) bad = "workspace must be 8-byte aligned";
+  if (bad) {
+    pfpp::set_error("%s: %s", func, bad);
+    return PFPP_EINVAL;
+  }
   hipStream_t st = pfpp::as_stream(stream);
   const int nn = (int)n, nblk = (nn + SK_ROWS - 1) / SK_ROWS;
   const SktWs w = skt_carve(workspace, n, nblk);
@@ -508,10 +546,10 @@ extern "C" int pfpp_sinkhorn_train_bwd(const float* s, int64_t ld, int64_t n, fl
   const float one = 1.0f;
   // G_T, in the layout whose sums step T - 1 needs: a row step (T - 1 even) reads row sums, a column step column sums
   if (max_iter == 0 || (max_iter - 1) % 2 == 0) {
-    hipLaunchKernelGGL(skt_bwd_rows_kernel<true>, rgrid, dim3(256), 0, st, s, ld, nn, tau, nullptr, nullptr, ds_mat, tgt, g, nullptr, ds, ldg,
+    hipLaunchKernelGGL((skt_bwd_rows_kernel<true, SEED>), rgrid, dim3(256), 0, st, s, ld, nn, tau, nullptr, nullptr, ds_mat, tgt, g, nullptr, ds, ldg,
                        max_iter == 0 ? tau : one, w.rs);
   } else {
-    hipLaunchKernelGGL(skt_bwd_cols_kernel<true>, cgrid, dim3(256), 0, st, s, ld, nn, tau, nullptr, nullptr, ds_mat, tgt, g, nullptr, ds, ldg, one,
+    hipLaunchKernelGGL((skt_bwd_cols_kernel<true, SEED>), cgrid, dim3(256), 0, st, s, ld, nn, tau, nullptr, nullptr, ds_mat, tgt, g, nullptr, ds, ldg, one,
                        w.ps);
     hipLaunchKernelGGL(skt_bwd_col_combine_kernel, dim3(fgrid), dim3(256), 0, st, w.ps, nn, nblk, w.cs);
   }
@@ -527,7 +565,20 @@ extern "C" int pfpp_sinkhorn_train_bwd(const float* s, int64_t ld, int64_t n, fl
                          one, w.rs);
     }
   }
-  return pfpp::check_launch(__func__);
+  return pfpp::check_launch(func);
+}
+}  // namespace
+
+extern "C" int pfpp_sinkhorn_train_bwd(const float* s, int64_t ld, int64_t n, float tau, int64_t max_iter, const int32_t* tgt,
+                                       const double* pots, const float* ds_mat, float g, float* ds, int64_t ldg, void* workspace,
+                                       int64_t workspace_bytes, pfpp_stream_t stream) {
+  return skt_bwd_run<false>(__func__, s, ld, n, tau, max_iter, tgt, pots, ds_mat, g, ds, ldg, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pfpp_sinkhorn_train_bwd_seeded(const float* s, int64_t ld, int64_t n, float tau, int64_t max_iter, const int32_t* tgt,
+                                              const double* pots, const float* ds_mat, float g, float* ds, int64_t ldg, void* workspace,
+                                              int64_t workspace_bytes, pfpp_stream_t stream) {
+  return skt_bwd_run<true>(__func__, s, ld, n, tau, max_iter, tgt, pots, ds_mat, g, ds, ldg, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pfpp_match_gt_targets(const float* gt_pcs, int64_t N, const int64_t* src, const int32_t* row_piece, const int64_t* puz_row_off,
@@ -566,6 +617,29 @@ extern "C" int pfpp_match_cls_bce(const float* logits, int64_t ldl, const uint8_
   long long* part_cnt = reinterpret_cast<long long*>(part_loss + CLS_BLOCKS);
   hipLaunchKernelGGL(match_cls_bce_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, ldl, labels, N, g, dlogit, ldd, part_loss, part_cnt);
   hipLaunchKernelGGL(match_cls_fold_kernel, dim3(1), dim3(64), 0, st, part_loss, part_cnt, nblk, N, loss, counts);
+  return pfpp::check_launch(__func__);
+}
+
+extern "C" int64_t pfpp_match_colsum_ordered_workspace(int64_t rows, int64_t cols) {
+  if (rows < 0 || cols < 1) return -1;
+  return ((rows + OC_ROWS - 1) / OC_ROWS) * cols * (int64_t)sizeof(double);
+}
+
+extern "C" int pfpp_match_colsum_ordered(const float* x, int64_t ld, int64_t rows, int64_t cols, float* out, void* workspace,
+                                         int64_t workspace_bytes, pfpp_stream_t stream) {
+  PFPP_REQUIRE(x && out, "null pointer");
+  PFPP_REQUIRE(rows >= 0 && cols >= 1 && ld >= cols, "bad sizes");
+  PFPP_SUPPORTED(cols <= 65536 && rows <= (int64_t)65535 * OC_ROWS, "more than 65536 columns or 4193280 rows");
+  PFPP_REQUIRE(rows == 0 || (workspace && workspace_bytes >= pfpp_match_colsum_ordered_workspace(rows, cols)),
+               "workspace smaller than pfpp_match_colsum_ordered_workspace(rows, cols)");
+  PFPP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "workspace must be 8-byte aligned");
+  hipStream_t st = pfpp::as_stream(stream);
+  const int64_t nblk = (rows + OC_ROWS - 1) / OC_ROWS;
+  const unsigned cblk = (unsigned)((cols + 255) / 256);
+  double* part = static_cast<double*>(workspace);
+  if (nblk > 0)
+    hipLaunchKernelGGL(match_colsum_part_kernel, dim3(cblk, (unsigned)nblk), dim3(256), 0, st, x, ld, rows, (int)cols, part);
+  hipLaunchKernelGGL(match_colsum_fold_kernel, dim3(cblk), dim3(256), 0, st, part, nblk, (int)cols, out);
   return pfpp::check_launch(__func__);
 }
 

@@ -354,6 +354,13 @@ SIGNATURES = {
     "pfpp_match_cls_bce": [_p, _i64, _p, _i64, _f32, _p, _p, _i64, _p, _p, _i64, _p],
     "pfpp_match_gather_raw": [_p, _p, _i64, _i64, _i64, _p, _p],
     "pfpp_match_scatter_raw": [_p, _p, _i64, _i64, _i64, C.c_int, _p, _p],
+    # ---- matcher head, training: the rigid term (csrc/matching_rigid.hip; the seeded backward in csrc/matching_train.hip)
+    "pfpp_rigid_pair_sums": [_p, _i64, _i64, _p, _p, _i64, _p, _p, _p],
+    "pfpp_rigid_pair_pose": [_i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "pfpp_rigid_fold": [_i64, _p, _p, C.c_double, _p, _p],
+    "pfpp_rigid_grad": [_i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
+    "pfpp_sinkhorn_train_bwd_seeded": [_p, _i64, _i64, _f32, _i64, _p, _p, _p, _f32, _p, _i64, _p, _i64, _p],
+    "pfpp_match_colsum_ordered": [_p, _i64, _i64, _i64, _p, _p, _i64, _p],
     # ---- matcher middle, training (csrc/matching_tf_train.hip)
     "pfpp_attn_rows16_train": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
     "pfpp_attn_rows16_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
@@ -400,6 +407,7 @@ PLAIN = {
     "pfpp_sinkhorn_workspace": ([_i64], C.c_int64),
     "pfpp_sinkhorn_train_workspace": ([_i64], C.c_int64),
     "pfpp_match_cls_bce_workspace": ([], C.c_int64),
+    "pfpp_match_colsum_ordered_workspace": ([_i64, _i64], C.c_int64),
 }
 
 # struct name in include/pfpp.h (without the pfpp_ prefix) -> its mirror here; load() compares the sizes

@@ -51,6 +51,7 @@ SOURCES = {
     "pointnet_ragged.hip": ["-ffp-contract=off"],
     "matching_tf.hip": ["-ffp-contract=off"],
     "matching_train.hip": ["-ffp-contract=off"],
+    "matching_rigid.hip": ["-ffp-contract=off"],
     "matching_tf_train.hip": ["-ffp-contract=off"],
     "matching_ptf_train.hip": ["-ffp-contract=off"],
     "pointnet_ragged_train.hip": ["-ffp-contract=off"],

@@ -3,12 +3,15 @@
 The training-time forward of the reference's Jigsaw_matching/model/jigsaw/joint_seg_align_model.py:164-268 behind the descriptor
 network, its _loss_function (:280-426), the backward of both and Adam (model/modules/matching_base_model.py:499-515):
 
-* sinkhorn_train / gt_targets / normalize_halves_bwd / cls_bce / gather_raw / scatter_raw: the kernels on their own.
+* sinkhorn_train / gt_targets / normalize_halves_bwd / cls_bce / gather_raw / scatter_raw / colsum_ordered: the kernels on their own.
 * MatchingHeadTrainEngine: one step over a ragged batch.  Both BatchNorms run on batch statistics (the affinity extractor's over the
   B N'_max rows of the zero-padded critical_feats, as in the reference), the critical points come from the ground-truth labels, s is
   not masked, no assignment is solved.  The Sinkhorn backward keeps max_iter potential vectors and one N' x N' matrix per puzzle
   where autograd keeps max_iter matrices.
 * MatchingHeadLoss: the engine as a torch.autograd.Function of part_feats.
+
+The rigid term of the loss (w_rig_loss, the reference's last 50 epochs) is matching_rigid.MatchingHeadRigidTrainEngine's: _step below
+takes that class's factory of a RigidBatch and then runs the per-puzzle loop in three stages.
 """
 from __future__ import annotations
 
@@ -78,19 +81,28 @@ def sinkhorn_train_fwd(s: torch.Tensor, tgt: torch.Tensor, *, tau: float = 0.05,
 
 
 def sinkhorn_train_bwd(s: torch.Tensor, tgt: torch.Tensor, pots: torch.Tensor, ds_mat: torch.Tensor, *, g: float = 1.0, tau: float = 0.05,
-                       max_iter: int = 20, padded: bool = False) -> torch.Tensor:
+                       max_iter: int = 20, padded: bool = False, seed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """g dLoss / ds of sinkhorn_train_fwd from the potentials it kept -> float32 [n, n]: a view of a buffer whose rows are padded to 4
-    floats with zeros, the layout the GEMMs read (padded=True returns that buffer, [n, (n + 3) & ~3])"""
+    floats with zeros, the layout the GEMMs read (padded=True returns that buffer, [n, (n + 3) & ~3]).  seed (float32 [n, (n + 3) & ~3],
+    zero padding columns): dLoss' / d ds_mat of a further term; the result is the gradient of both and is written over seed"""
     n = _check_s(s, tgt)
     _gpu(pots, torch.float64, "pots")
     _gpu(ds_mat, torch.float32, "ds_mat")
     if pots.shape != (max(int(max_iter), 1), n) or not pots.is_contiguous() or ds_mat.shape != (n, n) or not ds_mat.is_contiguous():
         raise ValueError("pots / ds_mat: not what sinkhorn_train_fwd returned for this s and max_iter")
     ldg = (n + 3) & ~3
+    ws = _sinkhorn_ws(n, s.device)
+    if seed is not None:
+        _gpu(seed, torch.float32, "seed")
+        if seed.shape != (n, ldg) or not seed.is_contiguous():
+            raise ValueError(f"seed: expected the padded buffer [{n}, {ldg}], got {tuple(seed.shape)}")
+        G = seed
+        check(_lib.load().pfpp_sinkhorn_train_bwd_seeded(_p(s), s.stride(0), n, float(tau), int(max_iter), _p(tgt), _p(pots), _p(ds_mat), float(g),
+                                                         _p(G), ldg, _p(ws), ws.numel() * 8, ops._stream()), "pfpp_sinkhorn_train_bwd_seeded")
+        return G if padded else G[:, :n]
     G = torch.empty((n, ldg), dtype=torch.float32, device=s.device)
     if ldg > n:
         G[:, n:].zero_()
-    ws = _sinkhorn_ws(n, s.device)
     check(_lib.load().pfpp_sinkhorn_train_bwd(_p(s), s.stride(0), n, float(tau), int(max_iter), _p(tgt), _p(pots), _p(ds_mat), float(g), _p(G), ldg,
                                               _p(ws), ws.numel() * 8, ops._stream()), "pfpp_sinkhorn_train_bwd")
     return G if padded else G[:, :n]
@@ -157,6 +169,22 @@ def scatter_raw(rows: torch.Tensor, idx: torch.Tensor, out: torch.Tensor, *, acc
     return out
 
 
+def colsum_ordered(x: torch.Tensor) -> torch.Tensor:
+    """out[c] = sum_r x[r, c] of x float32 [rows, cols] in a fixed order (fp64 partials per 64 rows, folded in order): the bias
+    gradients, which two runs of a step then give bit for bit (train_ops.colsum ends in float atomics)"""
+    _gpu(x, torch.float32, "x")
+    if x.dim() != 2 or (x.numel() and x.stride(1) != 1):
+        raise ValueError("colsum_ordered: x [rows, cols] with contiguous rows")
+    rows, cols = x.shape
+    if rows == 0:
+        return torch.zeros(cols, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    out = torch.empty(cols, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(lib.pfpp_match_colsum_ordered_workspace(rows, cols) // 8, 1), dtype=torch.float64, device=x.device)
+    check(lib.pfpp_match_colsum_ordered(_p(x), x.stride(0), rows, cols, _p(out), _p(ws), ws.numel() * 8, ops._stream()), "pfpp_match_colsum_ordered")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------ the engine
 PARAM_NAMES = ("pc_classifier.0.weight", "pc_classifier.0.bias", "pc_classifier.2.weight", "pc_classifier.2.bias",
                "affinity_extractor.0.weight", "affinity_extractor.0.bias", "affinity_extractor.2.weight", "affinity_extractor.2.bias",
@@ -169,13 +197,16 @@ class MatchingHeadTrainEngine:
     (head.gemm_mode, "f32" by default), tau and max_iter are the head's.  `saved` keeps the last step's intermediate tensors (the two
     ReLU outputs among them: the tests feed their sign pattern to the float64 reference)."""
 
+    _RIGID = False        # MatchingHeadRigidTrainEngine (matching_rigid.py) has the rigid term; this class refuses it
+
     def __init__(self, head: MatchingHead, *, w_cls_loss: float = 1.0, w_mat_loss: float = 0.0, w_rig_loss: float = 0.0):
-        if w_rig_loss > 0:
-            raise NotImplementedError("w_rig_loss > 0: rigid_loss solves an SVD per piece pair on the host (utils/loss.py:59) and is not built")
+        if w_rig_loss > 0 and not self._RIGID:
+            raise NotImplementedError("w_rig_loss > 0: rigid_loss (utils/loss.py:59) needs part_pcs, which this engine's loss_and_grads does not "
+                                      "take: use pfpp_hip.matching_rigid.MatchingHeadRigidTrainEngine")
         if head.gemm_mode != "f32":
             raise NotImplementedError("the head's training runs in the exact-fp32 GEMM mode only")
         self.head = head
-        self.w_cls_loss, self.w_mat_loss = float(w_cls_loss), float(w_mat_loss)
+        self.w_cls_loss, self.w_mat_loss, self.w_rig_loss = float(w_cls_loss), float(w_mat_loss), float(w_rig_loss)
         self.params: Dict[str, torch.nn.Parameter] = dict(head.named_parameters())
         if tuple(self.params) != PARAM_NAMES:
             raise ValueError(f"not a MatchingHead: parameters {list(self.params)}")
@@ -187,6 +218,13 @@ class MatchingHeadTrainEngine:
         """part_feats float32 [B, N, 128] (or a list / flat), gt_pcs float32 [..., 3] likewise, n_pcs int [B, P], part_valids [B, P];
         critical_label ([B, N] or flat, non-zero = critical) or the thresholds compute_label takes -> (loss_dict, d_part_feats [sum N, 128]).
         loss_dict has the reference's keys; its three losses are 0-dim fp64 tensors on the device (the sums they come from are fp64)"""
+        return self._step(part_feats, gt_pcs, n_pcs, part_valids, critical_label_thresholds, critical_label, None)
+
+    def _step(self, part_feats, gt_pcs, n_pcs, part_valids, critical_label_thresholds, critical_label, make_rigid):
+        """loss_and_grads; make_rigid (None, or a subclass's factory (counts, n_valid, row_off, src, device) -> an object with
+        pair_sums(b, ds_mat), pose_and_fold(w), grad(b), fold and records(): matching_rigid.RigidBatch) switches the rigid term on: the
+        per-puzzle loop then runs in three stages (forwards and pair sums, poses and fold, backwards) because the term's scale 1 / n_sum
+        is batch-global"""
         first = part_feats[0] if isinstance(part_feats, (list, tuple)) else part_feats
         _gpu(first, torch.float32, "part_feats")
         dev = first.device
@@ -236,7 +274,7 @@ class MatchingHeadTrainEngine:
         dlog_t = _tpad(dlog4)
         dw4 = _mm(dlog_t, h_c, torch.empty((4, PC_FEAT_DIM), **f32), M=4, N=PC_FEAT_DIM, K=N, lda=dlog_t.shape[1], ldw=PC_FEAT_DIM, ldc=PC_FEAT_DIM,
                   w_kmajor=True)
-        db4 = T.colsum(dlog4, torch.zeros(4, **f32))
+        db4 = colsum_ordered(dlog4)
         dgam, dbet = torch.zeros(PC_FEAT_DIM, **f32), torch.zeros(PC_FEAT_DIM, **f32)
         d_feats = bn_relu_bwd(feats, d_hc, mean_c, var_c, gam, bet, dgam, dbet, eps=bn.eps)
         grads.update({"pc_classifier.0.weight": dgam, "pc_classifier.0.bias": dbet, "pc_classifier.2.weight": dw4[0].reshape(1, PC_FEAT_DIM, 1),
@@ -264,6 +302,8 @@ class MatchingHeadTrainEngine:
                 grads[k] = zero_like(k)
             mat_loss = torch.zeros((), dtype=torch.float64, device=dev)
             loss_dict.update(mat_loss=mat_loss, N_=torch.tensor(0), loss=self.w_cls_loss * cls_loss[0])
+            if make_rigid is not None:                         # no pair at all: 0 / 0 in the reference's rigid term too
+                loss_dict["rig_loss"] = torch.zeros((), dtype=torch.float64, device=dev)
             self._store(grads)
             return loss_dict, d_feats
         src = torch.nonzero(labels).reshape(-1)                # global point index of every critical row: puzzle, piece, point order
@@ -294,23 +334,55 @@ class MatchingHeadTrainEngine:
         df = torch.zeros((Rp, AFF_FEAT_DIM), **f32)
         g_mat = self.w_mat_loss / R
         ds_mats = []
-        for b in range(B):
-            n = int(n_b[b])
-            if n == 0:                                         # a puzzle without critical points contributes nothing
-                ds_mats.append(torch.empty((0, 0), **f32))
-                continue
+
+        def forward(b, n):
             r0 = b * n_max
             t_b = tgt[row_off[b]:row_off[b + 1]]
             s = head.affinity(f, r0, r0 + n, pa)
             ds_mat, _, pots = sinkhorn_train_fwd(s, t_b, tau=head.tau, max_iter=head.max_iter, loss_out=losses[b:b + 1])
-            G = sinkhorn_train_bwd(s, t_b, pots, ds_mat, g=g_mat, tau=head.tau, max_iter=head.max_iter, padded=True)
-            ldg = G.shape[1]
+            return s, t_b, pots, ds_mat
+
+        def affinity_backward(b, n, G):
+            r0, ldg = b * n_max, G.shape[1]
             # dM = ds X2, into its rows of dpa; dX2^T = (X1 A)^T ds, which reads ds as it lies ([K, N]) and transposes [n, 256] matrices only
             _mm(G, f, dpa, M=n, N=HALF, K=n, lda=ldg, ldw=AFF_FEAT_DIM, ldc=HALF, w_kmajor=True, w_off=r0 * AFF_FEAT_DIM + HALF, c_off=r0 * HALF)
             pa_t = _tpad(pa[r0:r0 + n])
             dx2_t = _mm(pa_t, G, torch.empty((HALF, ldg), **f32), M=HALF, N=n, K=n, lda=ldg, ldw=ldg, ldc=ldg, w_kmajor=True)
             df[r0:r0 + n, HALF:] = dx2_t[:, :n].t()
-            ds_mats.append(ds_mat)
+
+        rigid = None
+        if make_rigid is None:
+            for b in range(B):
+                n = int(n_b[b])
+                if n == 0:                                     # a puzzle without critical points contributes nothing
+                    ds_mats.append(torch.empty((0, 0), **f32))
+                    continue
+                s, t_b, pots, ds_mat = forward(b, n)
+                G = sinkhorn_train_bwd(s, t_b, pots, ds_mat, g=g_mat, tau=head.tau, max_iter=head.max_iter, padded=True)
+                affinity_backward(b, n, G)
+                ds_mats.append(ds_mat)
+        else:
+            # the rigid term: its scale w_rig_loss / n_sum is a sum over the whole batch and stays on the device, so every puzzle's
+            # forward and pair sums come first, then the poses and the fold, then the backwards; s, pots and ds_mat are kept meanwhile
+            rigid = make_rigid(nc, n_valid, row_off, src, dev)
+            kept = []
+            for b in range(B):
+                n = int(n_b[b])
+                if n == 0:
+                    ds_mats.append(torch.empty((0, 0), **f32))
+                    kept.append(None)
+                    continue
+                kept.append(forward(b, n))
+                rigid.pair_sums(b, kept[b][3])
+                ds_mats.append(kept[b][3])
+            rigid.pose_and_fold(self.w_rig_loss)
+            for b in range(B):
+                if kept[b] is None:
+                    continue
+                s, t_b, pots, ds_mat = kept[b]
+                G = sinkhorn_train_bwd(s, t_b, pots, ds_mat, g=g_mat, tau=head.tau, max_iter=head.max_iter, padded=True, seed=rigid.grad(b))
+                affinity_backward(b, int(n_b[b]), G)
+                kept[b] = None
         mat_loss = losses.sum() / R
         # dX1 = dM A^T for all rows; dA = X1^T dM
         _mm(dpa, A.contiguous(), df, M=Rp, N=HALF, K=HALF, lda=HALF, ldw=HALF, ldc=AFF_FEAT_DIM)
@@ -322,7 +394,7 @@ class MatchingHeadTrainEngine:
         df_t = _tpad(df)
         dw_a = _mm(df_t, h_a, torch.empty((AFF_FEAT_DIM, PC_FEAT_DIM), **f32), M=AFF_FEAT_DIM, N=PC_FEAT_DIM, K=Rp, lda=df_t.shape[1], ldw=PC_FEAT_DIM,
                    ldc=PC_FEAT_DIM, w_kmajor=True)
-        db_a = T.colsum(df, torch.zeros(AFF_FEAT_DIM, **f32))
+        db_a = colsum_ordered(df)
         dgam_a, dbet_a = torch.zeros(PC_FEAT_DIM, **f32), torch.zeros(PC_FEAT_DIM, **f32)
         d_xg = bn_relu_bwd(xg, d_ha, mean_a, var_a, gam_a, bet_a, dgam_a, dbet_a, eps=bna.eps)
         scatter_raw(d_xg, pad_src, d_feats, accumulate=True)
@@ -330,6 +402,10 @@ class MatchingHeadTrainEngine:
                       "affinity_extractor.2.weight": dw_a.reshape(AFF_FEAT_DIM, PC_FEAT_DIM, 1), "affinity_extractor.2.bias": db_a, "affinity_layer.A": d_a})
         self.saved.update(h_aff=h_a, ds_mat=ds_mats, targets=tgt, row_off=row_off, pad_src=pad_src, n_critical_pcs=n_crit.reshape(B, P))
         loss_dict.update(mat_loss=mat_loss, N_=torch.tensor(n_max), loss=self.w_cls_loss * cls_loss[0] + self.w_mat_loss * mat_loss)
+        if rigid is not None:
+            rig_loss = rigid.fold[0].clone()
+            loss_dict.update(rig_loss=rig_loss, loss=loss_dict["loss"] + self.w_rig_loss * rig_loss)
+            self.saved.update(rigid.records())
         self._store(grads)
         return loss_dict, d_feats
 
@@ -353,8 +429,9 @@ class MatchingHeadTrainEngine:
 
 
 class MatchingHeadLoss(torch.autograd.Function):
-    """loss = MatchingHeadLoss.apply(part_feats, engine, gt_pcs, n_pcs, part_valids, critical_label_thresholds, critical_label): the
-    engine's loss as a function of part_feats [B, N, 128] or [sum N, 128].  loss.backward() hands engine's d_part_feats to whatever
+    """loss = MatchingHeadLoss.apply(part_feats, engine, gt_pcs, n_pcs, part_valids, critical_label_thresholds, critical_label[,
+    part_pcs]): the engine's loss as a function of part_feats [B, N, 128] or [sum N, 128]; the trailing part_pcs is handed to a
+    MatchingHeadRigidTrainEngine's loss_and_grads (its rigid term).  loss.backward() hands engine's d_part_feats to whatever
     produced part_feats and sets the head's parameters' .grad to this application's gradients times the incoming gradient (from copies
     kept at the forward, so a second backward over a retained graph sets the same values again).  Like loss_and_grads it OVERWRITES
     the .grad of the head's parameters, in forward and in backward: one application per optimizer step; two applications before a
@@ -362,9 +439,10 @@ class MatchingHeadLoss(torch.autograd.Function):
     engine.last_loss_dict holds the step's loss_dict (losses in fp64)."""
 
     @staticmethod
-    def forward(ctx, part_feats, engine, gt_pcs, n_pcs, part_valids, critical_label_thresholds=None, critical_label=None):
+    def forward(ctx, part_feats, engine, gt_pcs, n_pcs, part_valids, critical_label_thresholds=None, critical_label=None, part_pcs=None):
+        extra = {} if part_pcs is None else {"part_pcs": part_pcs}     # a MatchingHeadRigidTrainEngine's rigid term (matching_rigid.py)
         loss_dict, d_feats = engine.loss_and_grads(part_feats.detach(), gt_pcs, n_pcs, part_valids,
-                                                   critical_label_thresholds=critical_label_thresholds, critical_label=critical_label)
+                                                   critical_label_thresholds=critical_label_thresholds, critical_label=critical_label, **extra)
         engine.last_loss_dict = loss_dict
         ctx.engine, ctx.shape = engine, part_feats.shape
         ctx.grads = {k: (None if p.grad is None else p.grad.clone()) for k, p in engine.params.items()}
@@ -376,4 +454,4 @@ class MatchingHeadLoss(torch.autograd.Function):
         (d_feats,) = ctx.saved_tensors
         for k, p in ctx.engine.params.items():
             p.grad = None if ctx.grads[k] is None else ctx.grads[k] * grad_out.to(ctx.grads[k].dtype)
-        return (d_feats * grad_out.to(d_feats.dtype)).reshape(ctx.shape), None, None, None, None, None, None
+        return (d_feats * grad_out.to(d_feats.dtype)).reshape(ctx.shape), None, None, None, None, None, None, None

@@ -8,7 +8,13 @@ PyTorch-ROCm eager fp32 on the same GPU, restated the way the reference runs it:
 zero-padded critical_feats, the Sinkhorn that rewrites log_s 20 times, F.binary_cross_entropy against a dense gt_perm, torch.optim.Adam.
 The two alternate; reported are the medians of `--reps` wall times after one warm-up each, the engine's Sinkhorn backward alone by
 device events against the bytes its 21 passes must move (3 N'^2 4 B per update pass: s and G read, G written), and the peak device memory
-of both.  --profile runs only the engine's steps (for rocprofv3 --kernel-trace --stats)."""
+of both.  --profile runs only the engine's steps (for rocprofv3 --kernel-trace --stats).
+
+--rigid: the same puzzles with weights (1, 1, 1) (pfpp_hip.matching_rigid.MatchingHeadRigidTrainEngine; part_pcs = every piece's
+gt_pcs recentred and turned by a seeded rotation).  The eager step's rigid term is the reference's own procedure: a Python loop over
+the piece pairs that slices ds_mat, copies the block to the host, solves Horn's 4 x 4 eigenproblem in numpy and copies the pose back
+(tests/matching_rigid_cases.horn restates horn_87).  Also timed in the same run: the engine's step without the term, so that the
+term's added cost is visible.  The default mode is unchanged."""
 from __future__ import annotations
 
 import argparse
@@ -29,11 +35,40 @@ PIECES, PER_PIECE, MATCHES = 8, 625, 178
 TAU, ITERS = 0.05, 20
 
 
-def load_cases():
-    spec = importlib.util.spec_from_file_location("matching_cases", ROOT / "tests" / "matching_cases.py")
+def load_cases(stem: str = "matching_cases"):
+    spec = importlib.util.spec_from_file_location(stem, ROOT / "tests" / f"{stem}.py")
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def eager_rigid_loss(mats, part_pcs, label, piece, n_pieces, horn):
+    """utils/loss.py:59-142 the way the reference runs it: per pair, the block to the host, Horn in numpy (float32 inputs), the pose back"""
+    dev = mats[0].device
+    loss, n_sum = torch.zeros((), device=dev), 0
+    for b, mat in enumerate(mats):
+        pts, pc = part_pcs[b, label[b]], piece[b, label[b]].cpu().numpy()
+        off = np.concatenate([[0], np.cumsum(np.bincount(pc, minlength=n_pieces))])
+        mat_d = mat.detach().cpu().numpy()
+        total = torch.sum(mat)
+        for p in range(n_pieces):
+            for q in range(p + 1, n_pieces):
+                i0, i1, j0, j1 = off[p], off[p + 1], off[q], off[q + 1]
+                if i1 == i0 or j1 == j0:
+                    continue
+                w = mat[i0:i1, j0:j1] + mat[j0:j1, i0:i1].transpose(1, 0)
+                mat_s = torch.sum(w)
+                if n_pieces > 2 and mat_s == 0 and total > 0:
+                    continue
+                src, tgt = pts[i0:i1], pts[j0:j1]
+                R, t, _, _ = horn(src.cpu().numpy(), tgt.cpu().numpy(), mat_d[i0:i1, j0:j1] + mat_d[j0:j1, i0:i1].T)
+                rot = torch.tensor(R.astype(np.float32), device=dev)
+                trans = torch.tensor(t.astype(np.float32), device=dev)
+                a = (torch.matmul(rot, src.transpose(1, 0)).transpose(1, 0) + trans) * torch.sum(w, dim=-1).reshape(-1, 1)
+                c = torch.matmul(w, tgt)
+                n_sum += int(i1 - i0)
+                loss = loss + torch.sum(a ** 2 + c ** 2 - 2 * a * c) * mat_s
+    return loss / n_sum
 
 
 class EagerHead(torch.nn.Module):
@@ -49,8 +84,9 @@ class EagerHead(torch.nn.Module):
         self.affinity_extractor.load_state_dict({k[len("affinity_extractor."):]: v for k, v in sd.items() if k.startswith("affinity_extractor.")})
         self.train()
 
-    def loss(self, feats, gt_pcs, label, piece):
-        """feats [B, N, 128], gt_pcs [B, N, 3], label bool [B, N], piece int64 [B, N]"""
+    def loss(self, feats, gt_pcs, label, piece, rigid=None):
+        """feats [B, N, 128], gt_pcs [B, N, 3], label bool [B, N], piece int64 [B, N]; rigid = (part_pcs, n_pieces, horn) adds the
+        rigid term"""
         F = torch.nn.functional
         B, N, _ = feats.shape
         logits = self.pc_classifier(feats.transpose(1, 2)).transpose(1, 2).reshape(-1)
@@ -76,13 +112,17 @@ class EagerHead(torch.nn.Module):
             d = d + same * 1e6
             gt_perm = torch.zeros(B, n_max, n_max, device=feats.device).scatter_(2, d.argmin(-1, keepdim=True), 1) * (~same)
         total = torch.zeros((), device=feats.device)
+        mats = []
         for b in range(B):
             n = int(n_sum[b])
             log_s = s[b, :n, :n] / TAU
             for i in range(ITERS):
                 log_s = log_s - torch.logsumexp(log_s, 1 if i % 2 == 0 else 0, keepdim=True)
-            total = total + F.binary_cross_entropy(torch.exp(log_s), gt_perm[b, :n, :n], reduction="sum")
-        return cls_loss + total / n_sum.sum()
+            mats.append(torch.exp(log_s))
+            total = total + F.binary_cross_entropy(mats[b], gt_perm[b, :n, :n], reduction="sum")
+        if rigid is None:
+            return cls_loss + total / n_sum.sum()
+        return cls_loss + total / n_sum.sum() + eager_rigid_loss(mats, rigid[0], label, piece, rigid[1], rigid[2])
 
 
 def main() -> int:
@@ -91,6 +131,7 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-eager", action="store_true")
     ap.add_argument("--profile", action="store_true", help="only the engine's steps (kernel trace)")
+    ap.add_argument("--rigid", action="store_true", help="weights (1, 1, 1): the step with the rigid term")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -107,6 +148,11 @@ def main() -> int:
     head.load_state_dict(sd, strict=True)
     head.to(dev)
     eng = MatchingHeadTrainEngine(head, w_cls_loss=1.0, w_mat_loss=1.0)
+    if args.rigid:
+        from pfpp_hip.matching_rigid import MatchingHeadRigidTrainEngine
+
+        plain_eng = eng
+        eng = MatchingHeadRigidTrainEngine(head, w_cls_loss=1.0, w_mat_loss=1.0, w_rig_loss=1.0)
     sym = [(p, p + 1, MATCHES) for p in range(PIECES - 1)]
     pzs = [cases.build_puzzle([PER_PIECE] * PIECES, sym, [], 100 + k) for k in range(args.puzzles)]
     feats = torch.from_numpy(np.stack([p["part_feats"] for p in pzs])).to(dev)
@@ -116,9 +162,14 @@ def main() -> int:
     valids = np.stack([p["part_valids"] for p in pzs])
     piece = torch.from_numpy(np.stack([np.repeat(np.arange(n_pcs.shape[1]), n) for n in n_pcs])).to(dev)
     n_prime = [int(x) for x in label.sum(1).tolist()]
+    extra, rigid = {}, None
+    if args.rigid:
+        rcases = load_cases("matching_rigid_cases")
+        part_pcs = torch.from_numpy(rcases.make_part_pcs({"gt_pcs": gt_pcs.cpu().numpy(), "n_pcs": n_pcs})).to(dev)
+        extra, rigid = {"part_pcs": part_pcs}, (part_pcs, PIECES, rcases.horn)
 
     def hip_step():
-        loss_dict, _ = eng.loss_and_grads(feats, gt_pcs, n_pcs, valids, critical_label=label)
+        loss_dict, _ = eng.loss_and_grads(feats, gt_pcs, n_pcs, valids, critical_label=label, **extra)
         eng.optimizer_step()
         return loss_dict["loss"]
 
@@ -142,7 +193,7 @@ def main() -> int:
 
     def eager_step():
         opt.zero_grad(set_to_none=True)
-        loss = eager.loss(feats, gt_pcs, label, piece)
+        loss = eager.loss(feats, gt_pcs, label, piece, rigid)
         loss.backward()
         opt.step()
         return loss
@@ -164,6 +215,28 @@ def main() -> int:
         times["hip"].append(wall(hip_step)[1])
         if eager is not None:
             times["eager"].append(wall(eager_step)[1])
+    if args.rigid:
+        def plain_step():
+            loss_dict, _ = plain_eng.loss_and_grads(feats, gt_pcs, n_pcs, valids, critical_label=label)
+            plain_eng.optimizer_step()
+            return loss_dict["loss"]
+
+        plain_step()
+        plain = [wall(plain_step)[1] for _ in range(args.reps)]
+        saved = eng.saved
+        line = {"bench": "matching_head_train_rigid", "puzzles": args.puzzles, "points": PIECES * PER_PIECE, "n_critical": n_prime,
+                "pairs": int(saved["kept"].numel()), "pairs_kept": int(saved["kept"].sum()), "hip_step_ms": statistics.median(times["hip"]),
+                "hip_step_ms_without_rigid": statistics.median(plain), "rigid_added_ms": statistics.median(times["hip"]) - statistics.median(plain),
+                "hip_loss_after_warmup": peak["hip_loss"], "hip_peak_step_mem_mb": peak["hip"],
+                "extra_passes_must_move_mb_per_puzzle": 3 * n_prime[0] * n_prime[0] * 4 / 1e6}
+        if eager is not None:
+            line.update({"eager_step_ms": statistics.median(times["eager"]), "eager_loss_after_warmup": peak["eager_loss"],
+                         "eager_peak_step_mem_mb": peak["eager"], "speedup_vs_eager": statistics.median(times["eager"]) / statistics.median(times["hip"])})
+        text = json.dumps(line)
+        print(text)
+        if args.out:
+            Path(args.out).write_text(text + "\n")
+        return 0
     # the Sinkhorn of one puzzle on its own, by device events
     n = n_prime[0]
     s = (0.3 * torch.randn(n, n, device=dev)).contiguous()
