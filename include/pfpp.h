@@ -1521,6 +1521,40 @@ int pfpp_ragged_group_bwd(const float* dA, int64_t lda, int64_t D, const int64_t
 int pfpp_ragged_interp_bwd(const float* dout, int64_t ldo, int64_t D1, int64_t D2, const float* weights, const int64_t* off, const int32_t* ent,
                            int64_t N, int64_t S, float* dpoints2, double* workspace, pfpp_stream_t stream);
 
+/* ---- matcher, evaluation: piece-pair poses by RANSAC and the ragged nearest distance (Jigsaw_matching/utils/estimate_transform.py:8-66
+ * called at model/modules/matching_base_model.py:338; utils/eval_utils.py's chamfer terms; csrc/matching_pose.hip).  The reference gives
+ * one piece pair at a time to open3d's registration_ransac_based_on_correspondence on the host (ransac_n = 3, 50,000 draws at most, early
+ * stop by confidence); here all H hypotheses of all E pairs of a batch are scored in one launch, every one of them, with counter-based
+ * draws.
+ * pfpp_ransac_pairs: pts float32 [R, 3]; pair_off int64 [E, 2] = the first rows of pair e's source and target piece in pts; corr int32
+ * [corr_off[E], 2] = (i, j), piece-local: correspondence k of pair e (corr_off int64 [E + 1], M_e = corr_off[e + 1] - corr_off[e] >= 3)
+ * matches S_k = pts[pair_off[e, 0] + i] to T_k = pts[pair_off[e, 1] + j].  Hypothesis h < H of pair e: (x0, x1, x2, -) =
+ * Philox4x32-10(key = (seed & 0xffffffff, seed >> 32), counter = (h, e, 0, 0)); i0 = mulhi32(x0, M), i1 = mulhi32(x1, M - 1), plus one
+ * if >= i0, i2 = mulhi32(x2, M - 2), plus one if >= min(i0, i1), then plus one if >= max(i0, i1).  Its pose is Horn's closed form
+ * (pairwise_alignment.py:11-79) with unit weights on the three correspondences in fp64: centroids, M = sum (S - cS) (T - cT)^T, N,
+ * the ten-sweep Jacobi of pfpp_rigid_pair_pose, the eigenvector of the first of the largest eigenvalues, t = cT - R cS.  Its score:
+ * count = #{k : |R S_k + t - T_k|^2 < max_dist^2} and sumsq = the sum of those squared distances in correspondence order, fp64.  A
+ * hypothesis whose two largest eigenvalues differ by no more than 1e-9 max |N_ij| is degenerate and scores count = -1.  The winner has
+ * the largest count, then the smallest sumsq, then the smallest h: a total order, so the result does not depend on the grid.
+ * Outputs per pair: Rout [E, 9], tout [E, 3] (fp32, rounded once from fp64); stats fp64 [E, 2] = (sumsq, the inliers the refinement
+ * used); info int32 [E, 3] = (best h, count, status).  status bit 0: a non-degenerate winner exists - otherwise R = 1, t = cT - cS over
+ * all correspondences, h = count = -1; bit 1 (refine != 0 only): the pose is Horn's over the winner's inliers (unit weights, fp64 sums
+ * in a fixed order) - not set, and the three-point pose kept, when fewer than 3 inliers or a degenerate N.  count and sumsq are the
+ * three-point pose's either way.  counts_out int32 [E, H] (may be null; tests): every hypothesis's count.  The matched points are
+ * staged PFPP_RANSAC_TILE correspondences at a time; a larger pair is walked in tiles.  Indices are clamped into pts for memory safety
+ * only.  workspace: pfpp_ransac_pairs_workspace(E, H) bytes (-1 for E < 0 or H < 1), 8-byte aligned.  E = 0 launches nothing.
+ * pfpp_nn_dist_ragged: pfpp_nn_dist over `segments` segments of unequal sizes in one launch: for i in [src_off[s], src_off[s + 1]):
+ * out[i] = min over j in [dst_off[s], dst_off[s + 1]) of |src[i] - dst[j]|^2, bit for bit pfpp_nn_dist's arithmetic; +inf where the
+ * segment has no target; an empty segment writes nothing.  src_off, dst_off int64 [segments + 1] on the device; max_n >= the longest
+ * source segment (it sizes the grid).                                                                                              */
+#define PFPP_RANSAC_TILE 1024
+int64_t pfpp_ransac_pairs_workspace(int64_t E, int64_t H);
+int pfpp_ransac_pairs(const float* pts, int64_t R, int64_t E, const int64_t* pair_off, const int32_t* corr, const int64_t* corr_off, int64_t H,
+                      double max_dist, uint64_t seed, int refine, float* Rout, float* tout, double* stats, int32_t* info, int32_t* counts_out,
+                      void* workspace, int64_t workspace_bytes, pfpp_stream_t stream);
+int pfpp_nn_dist_ragged(const float* src, const int64_t* src_off, const float* dst, const int64_t* dst_off, float* out, int64_t segments,
+                        int64_t max_n, pfpp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,19 +13,20 @@
 //    are folded in order at the end.  fp64 sums of exact fp64 sums of two fp32 entries.  The workgroups of the diagonal blocks only
 //    look for a positive entry (the reference's `sum(ds_mat[b]) > 0`, which for non-negative entries is `any > 0`).
 //  * rigid_pair_pose_kernel — a wave per pair of the whole batch: mat_s, the centroids, M, Horn's N, a cyclic Jacobi of ten sweeps
-//    from the identity in fp64, the eigenvector of the first of the largest eigenvalues, R and t (fp32), pair_loss.
+//    from the identity in fp64, the eigenvector of the first of the largest eigenvalues, R and t (fp32), pair_loss.  N, the
+//    Jacobi and the quaternion's rotation are horn_common.h's, shared with matching_pose.hip.
 //  * rigid_fold_kernel — numerator and n_sum over the pairs in pair order, rig_loss and the gradient scale w_rig_loss / n_sum.
 //  * rigid_grad_kernel — d(w_rig_loss rig_loss) / d ds_mat for one puzzle, element-wise: with a the index in the earlier piece and
 //    c the one in the later, scale (2 mat_s e_a . (A_a - T_c) + pair_loss); exact zeros in diagonal blocks and in pairs not kept.
 // All sums fp64, no float atomics, every fold in a fixed order: two runs agree bitwise.
 #include "pfpp_common.h"
+#include "horn_common.h"
 
 namespace {
 
 constexpr int RG_TILE = 64;          // rows per workgroup and columns per step of the pair sums
 constexpr int RG_PMAX = 64;          // pieces per puzzle the kernels are built for (the reference has at most 20)
 constexpr int RG_STATS = 8;          // doubles per pair record: mat_s, pair_loss, the four eigenvalues (ascending), n1, n2
-constexpr int RG_SWEEPS = 10;        // cyclic Jacobi sweeps on the 4 x 4: quadratic convergence, six suffice in fp64
 
 __device__ __forceinline__ double rg_wave_sum(double v) {
 #pragma unroll
@@ -102,33 +103,6 @@ __global__ __launch_bounds__(256) void rigid_pair_sums_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------ pair pose and loss
-// one Jacobi rotation of the symmetric A (full storage) in the plane (P_, Q_), accumulated into the eigenvector matrix V
-template <int P_, int Q_>
-__device__ __forceinline__ void rg_rotate(double (&A)[4][4], double (&V)[4][4]) {
-  const double apq = A[P_][Q_];
-  if (apq == 0.0) return;
-  const double theta = (A[Q_][Q_] - A[P_][P_]) / (2.0 * apq);
-  const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {                                      // columns P_, Q_ of A and of V
-    const double akp = A[k][P_], akq = A[k][Q_];
-    A[k][P_] = c * akp - s * akq;
-    A[k][Q_] = s * akp + c * akq;
-    const double vkp = V[k][P_], vkq = V[k][Q_];
-    V[k][P_] = c * vkp - s * vkq;
-    V[k][Q_] = s * vkp + c * vkq;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {                                      // rows P_, Q_ of A
-    const double apk = A[P_][k], aqk = A[Q_][k];
-    A[P_][k] = c * apk - s * aqk;
-    A[Q_][k] = s * apk + c * aqk;
-  }
-  A[P_][Q_] = 0.0;
-  A[Q_][P_] = 0.0;
-}
-
 // pairs int32 [npairs, 4] = (puzzle, p, q, -); puz_row_off int64 [B + 1] into pts [R, 3] and rb [R, P, 4]; piece_off int32
 // [B, P + 1] puzzle-local; status: 1 kept, 0 skipped (the reference's `continue`), -1 not finite in the reference (mat_s == 0 kept)
 __global__ __launch_bounds__(64) void rigid_pair_pose_kernel(const int32_t* __restrict__ pairs, const int64_t* __restrict__ puz_row_off,
@@ -196,47 +170,10 @@ __global__ __launch_bounds__(64) void rigid_pair_pose_kernel(const int32_t* __re
     for (int c = 0; c < 3; ++c) M[a][c] = rg_wave_sum(M[a][c]);
 
   // Horn's N (pairwise_alignment.py:20-47) and its eigenvectors; every lane holds the same numbers
-  double A[4][4], V[4][4];
-  A[0][0] = (M[0][0] + M[1][1]) + M[2][2];
-  A[1][1] = (M[0][0] - M[1][1]) - M[2][2];
-  A[2][2] = (M[1][1] - M[0][0]) - M[2][2];
-  A[3][3] = (M[2][2] - M[0][0]) - M[1][1];
-  A[0][1] = A[1][0] = M[1][2] - M[2][1];
-  A[0][2] = A[2][0] = M[2][0] - M[0][2];
-  A[0][3] = A[3][0] = M[0][1] - M[1][0];
-  A[1][2] = A[2][1] = M[0][1] + M[1][0];
-  A[1][3] = A[3][1] = M[0][2] + M[2][0];
-  A[2][3] = A[3][2] = M[1][2] + M[2][1];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) V[a][c] = a == c ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < RG_SWEEPS; ++sweep) {
-    rg_rotate<0, 1>(A, V); rg_rotate<0, 2>(A, V); rg_rotate<0, 3>(A, V);
-    rg_rotate<1, 2>(A, V); rg_rotate<1, 3>(A, V); rg_rotate<2, 3>(A, V);
-  }
-  double ev[4] = {A[0][0], A[1][1], A[2][2], A[3][3]};
-  double qv[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
-  double best = ev[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    if (ev[k] > best) {                                              // strict: the first of equal maxima
-      best = ev[k];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) qv[a] = V[a][k];
-    }
-  }
-  const double q0 = qv[0], q1 = qv[1], q2 = qv[2], q3 = qv[3];
-  double Rd[3][3];
-  Rd[0][0] = ((q0 * q0 + q1 * q1) - q2 * q2) - q3 * q3;
-  Rd[0][1] = 2.0 * (q1 * q2 - q0 * q3);
-  Rd[0][2] = 2.0 * (q1 * q3 + q0 * q2);
-  Rd[1][0] = 2.0 * (q2 * q1 + q0 * q3);
-  Rd[1][1] = ((q0 * q0 - q1 * q1) + q2 * q2) - q3 * q3;
-  Rd[1][2] = 2.0 * (q2 * q3 - q0 * q1);
-  Rd[2][0] = 2.0 * (q3 * q1 - q0 * q2);
-  Rd[2][1] = 2.0 * (q3 * q2 + q0 * q1);
-  Rd[2][2] = ((q0 * q0 - q1 * q1) - q2 * q2) + q3 * q3;
+  double A[4][4], V[4][4], ev[4], qv[4], Rd[3][3];
+  rg_horn_n(M, A);
+  (void)rg_top_eigenvector(A, V, ev, qv);
+  rg_quat_rot(qv, Rd);
   // t = sum_i (b_i - r_i R S_i) / mat_s; R and t are handed on rounded to fp32 (pairwise_alignment.py:79)
   const bool zero = mat_s == 0.0;
   float Rf[3][3], tf[3];

@@ -382,6 +382,9 @@ SIGNATURES = {
     "pfpp_ragged_bn_relu_bwd": [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p],
     "pfpp_ragged_group_bwd": [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, C.c_int, _p],
     "pfpp_ragged_interp_bwd": [_p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p],
+    # ---- matcher, evaluation: pairwise RANSAC and the ragged nearest distance (csrc/matching_pose.hip)
+    "pfpp_ransac_pairs": [_p, _i64, _i64, _p, _p, _p, _i64, C.c_double, C.c_uint64, C.c_int, _p, _p, _p, _p, _p, _p, _i64, _p],
+    "pfpp_nn_dist_ragged": [_p, _p, _p, _p, _p, _i64, _i64, _p],
 }
 PLAIN = {
     "pfpp_version": ([], C.c_int),
@@ -408,6 +411,7 @@ PLAIN = {
     "pfpp_sinkhorn_train_workspace": ([_i64], C.c_int64),
     "pfpp_match_cls_bce_workspace": ([], C.c_int64),
     "pfpp_match_colsum_ordered_workspace": ([_i64, _i64], C.c_int64),
+    "pfpp_ransac_pairs_workspace": ([_i64, _i64], C.c_int64),
 }
 
 # struct name in include/pfpp.h (without the pfpp_ prefix) -> its mirror here; load() compares the sizes

@@ -33,11 +33,13 @@ def list_puzzles(features: str, out: str):
     return sorted(todo), sorted(skipped)
 
 
-def load_features(features: str, data_id: int, points: bool = False):
-    """one puzzle's file: the descriptors (part_feats [N_sum, 128]) or, with points, the point clouds (part_pcs [N_sum, 3])"""
+def load_features(features: str, data_id: int, points: bool = False, extra=()):
+    """one puzzle's file: the descriptors (part_feats [N_sum, 128]) or, with points, the point clouds (part_pcs [N_sum, 3]); extra:
+    further entries the caller needs (they must be there)"""
     import numpy as np
 
     keys, first, width = (POINT_KEYS, "part_pcs", 3) if points else (FEATURE_KEYS, "part_feats", 128)
+    keys = tuple(keys) + tuple(k for k in extra if k not in keys)
     path = os.path.join(features, f"{data_id}.npz")
     with np.load(path) as d:
         missing = [k for k in keys if k not in d.files]
@@ -48,6 +50,31 @@ def load_features(features: str, data_id: int, points: bool = False):
     if x[first].shape != (n, width) or x["gt_pcs"].shape != (n, 3) or x["n_pcs"].shape != x["part_valids"].shape:
         raise ValueError(f"{path}: {first} {x[first].shape}, gt_pcs {x['gt_pcs'].shape} do not match n_pcs (sum {n})")
     return x
+
+
+def head_batches(source: str, points: bool, checkpoint: str, gemm: str, seed: int, todo, batch_size: int, extra=(), dense_perm: bool = False):
+    """the models of a checkpoint over the puzzles `todo` of a directory, batch by batch: pfpp_hip.matching.DescriptorNetwork in
+    front of the head when the files hold points, the head alone when they hold descriptors
+    -> yields (data ids, the puzzles' files, n_pcs [b, P], part_valids [b, P], the head's output)"""
+    import numpy as np
+    import torch
+
+    from pfpp_hip.matching import DescriptorNetwork, MatchingHead
+
+    head = MatchingHead.from_checkpoint(checkpoint, gemm_mode=gemm).cuda()
+    net = DescriptorNetwork.from_checkpoint(checkpoint, gemm_mode=gemm).cuda() if points else None
+    for i in range(0, len(todo), batch_size):
+        ids = todo[i:i + batch_size]
+        items = [load_features(source, d, points=net is not None, extra=extra) for d in ids]
+        P = max(x["n_pcs"].shape[0] for x in items)
+        pad = lambda a: np.concatenate([np.asarray(a).reshape(-1), np.zeros(P - a.shape[0], dtype=a.dtype)])
+        n_pcs, valids = np.stack([pad(x["n_pcs"].astype(np.int64)) for x in items]), np.stack([pad(x["part_valids"].astype(np.float32)) for x in items])
+        if net is not None:          # descriptors of the whole batch, flat, as the head takes them
+            feats = net([torch.from_numpy(np.ascontiguousarray(x["part_pcs"], dtype=np.float32)).cuda() for x in items], n_pcs, valids,
+                        seed=seed + i)
+        else:
+            feats = [torch.from_numpy(np.ascontiguousarray(x["part_feats"], dtype=np.float32)).cuda() for x in items]
+        yield ids, items, n_pcs, valids, head(feats, n_pcs, valids, dense_perm=dense_perm)
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -81,23 +108,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     if not torch.cuda.is_available():
         print("generate_matching_data: no GPU: the matching kernels run on the GPU only", file=sys.stderr)
         return 2
-    from pfpp_hip.matching import DescriptorNetwork, MatchingHead, match_edges, write_matching_data
+    from pfpp_hip.matching import match_edges, write_matching_data
 
-    head = MatchingHead.from_checkpoint(args.checkpoint, gemm_mode=args.gemm).cuda()
-    net = DescriptorNetwork.from_checkpoint(args.checkpoint, gemm_mode=args.gemm).cuda() if args.points is not None else None
     t0, n, host = time.perf_counter(), 0, 0.0
-    for i in range(0, len(todo), args.batch_size):
-        ids = todo[i:i + args.batch_size]
-        items = [load_features(source, d, points=net is not None) for d in ids]
-        P = max(x["n_pcs"].shape[0] for x in items)
-        pad = lambda a: np.concatenate([np.asarray(a).reshape(-1), np.zeros(P - a.shape[0], dtype=a.dtype)])
-        n_pcs, valids = np.stack([pad(x["n_pcs"].astype(np.int64)) for x in items]), np.stack([pad(x["part_valids"].astype(np.float32)) for x in items])
-        if net is not None:          # descriptors of the whole batch, flat, as the head takes them
-            feats = net([torch.from_numpy(np.ascontiguousarray(x["part_pcs"], dtype=np.float32)).cuda() for x in items], n_pcs, valids,
-                        seed=args.seed + i)
-        else:
-            feats = [torch.from_numpy(np.ascontiguousarray(x["part_feats"], dtype=np.float32)).cuda() for x in items]
-        out = head(feats, n_pcs, valids, dense_perm=False)
+    for ids, items, n_pcs, valids, out in head_batches(source, args.points is not None, args.checkpoint, args.gemm, args.seed, todo, args.batch_size):
         host += out.timings["host_assignment_s"]
         nc = out.n_critical_pcs.cpu().numpy()
         for b, (d, x) in enumerate(zip(ids, items)):
