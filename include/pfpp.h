@@ -1200,6 +1200,48 @@ int pfpp_mesh_vertex_graph(const double* verts, const int64_t* vert_off, const i
                            pfpp_stream_t stream);
 int pfpp_mesh_status(const uint64_t* status, pfpp_stream_t stream);
 
+/* ---- the matcher's training batches from a resident mesh store (Jigsaw_matching/dataset/all_piece_matching_dataset.py;
+ * csrc/matching_dataset.hip) ------------------------------------------------------------------------------------------------------
+ * The store is the CSR batch above over the S puzzles of a whole split (store_part_off = its puz_part_off [S + 1], store_data_id
+ * = its data_id [S]) with cdf and total of one pfpp_mesh_face_cdf call.  sel int64 [B] picks the puzzles of a batch (device; a
+ * repeated index is allowed, the caller refuses indices outside [0, S)).  Every puzzle gets exactly num_points rows: puzzle b of
+ * the batch owns rows [b num_points, (b + 1) num_points) of every [B num_points, .] output, so no size depends on the device.
+ * Failures found on the device go into `status` (pfpp_mesh_status): a part whose area is zero or not finite, a selection outside
+ * the store, parts x min_part_point > num_points, an order entry outside its piece.  max_parts <= 32.
+ * pfpp_mdata_piece_counts: sample_reweighted_points_by_areas (:164-193) with areas = total: np.sum in numpy's order (below 8
+ * values in sequence; else eight running sums over blocks of 8 folded ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the rest in sequence),
+ * nps = int32(ceil(areas num_points / sum)), the first argmax absorbs sum(nps) - num_points, then (min_part_point > 1) pieces below
+ * min_part_point are raised to it and `while delta > 0` takes the excess from the first argmax, both branches.  n_pcs int64
+ * [B, max_parts] (zeros behind the puzzle's parts), piece_off int64 [B max_parts + 1] (row offsets, empty slots as empty ranges),
+ * puz_piece_off int64 [B + 1] = b max_parts: the layout the matcher's head and encoder take.
+ * pfpp_mdata_sample: _get_pcs's mesh.sample (:217-220) for row r of puzzle b: its piece and local row j from piece_off, sample
+ * index s = order[b, r] (int32 [B, num_points], the reference's _shuffle_pc :141-148) or j; uniforms (u0, l0, l1) = u[b, o + s]
+ * (float64 [B, num_points, 3], piece order, o = the piece's first row) or (pfpp_rng_u64(seed, split, idx) >> 11) 2^-53 with
+ * idx = ((data_id max_parts + slot) num_points + s) 3 + k.  `split` carries the split and the epoch: split = (epoch << 1) | s
+ * with s = 0 for train and 1 for val, epoch < 2^31.  The face search and the fold are pfpp_mesh_sample_surface's.  points fp64
+ * [B, num_points, 3] (workspace) holds the sample at row o + s; gt_pcs float32 [B num_points, 3] = float32(point) at row r;
+ * face_idx int32 [B num_points] is optional.
+ * pfpp_mdata_pose: _recenter_pc and _rotate_pc (:117-139) per piece slot: c = (rows o .. o + n - 1 of points added in row order) / n,
+ * part_trans float32 [B max_parts, 3] = c; part_pcs float32 [B num_points, 3] row o + j = float32((R0 x + R1 y) + R2 z) per output
+ * coordinate, (x, y, z) = points[o + s] - c, no contraction.  rot float64 [B max_parts, 3, 3] gives R (part_quat is then the
+ * caller's and may be NULL); with rot NULL R is the matrix of a quaternion (w, x, y, z) = (x1, x2, y1 f, y2 f), f = sqrt((1 - s1)
+ * / s2), drawn by Marsaglia's rejection: attempt t < 64 reads c = 2 U(idx + 0) - 1, d = 2 U(idx + 1) - 1 for the first pair (kept
+ * when c c + d d < 1) and idx + 2, idx + 3 for the second (kept when 0 < s < 1), idx = ((data_id max_parts + slot) 64 + t) 4, U
+ * keyed by (seed ^ 0xA5B85C5E198ED849, split); a pair with no attempt inside gives the identity.  part_quat float32
+ * [B max_parts, 4] = (w, -x, -y, -z), the quaternion of R^T (:136).  Empty slots get zeros.  rot_out float64 [B max_parts, 3, 3]
+ * (optional) receives R.                                                                                                         */
+int pfpp_mdata_piece_counts(const double* total, const int64_t* store_part_off, const int64_t* sel, int64_t B, int64_t S,
+                            int64_t num_points, int64_t min_part_point, int64_t max_parts, int64_t* n_pcs, int64_t* piece_off,
+                            int64_t* puz_piece_off, uint64_t* status, pfpp_stream_t stream);
+int pfpp_mdata_sample(const double* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* face_off, const double* cdf,
+                      const double* total, const int64_t* store_part_off, const int64_t* store_data_id, const int64_t* sel,
+                      const int64_t* piece_off, int64_t B, int64_t S, int64_t num_points, int64_t max_parts, const int32_t* order,
+                      const double* u, uint64_t seed, uint32_t split, double* points, float* gt_pcs, int32_t* face_idx, uint64_t* status,
+                      pfpp_stream_t stream);
+int pfpp_mdata_pose(const double* points, const int64_t* piece_off, const int64_t* store_data_id, const int64_t* sel, int64_t B,
+                    int64_t S, int64_t num_points, int64_t max_parts, const int32_t* order, const double* rot, uint64_t seed,
+                    uint32_t split, float* part_pcs, float* part_quat, float* part_trans, double* rot_out, pfpp_stream_t stream);
+
 /* ---- matcher back end: descriptors -> matching_data (Jigsaw_matching/; csrc/matching.hip) ---------------------------------------
  * Batch layout: the points of all puzzles flat, [N, 128] descriptors / [N, 3] coordinates; piece_off int64 [Pt + 1] are the point
  * offsets of the Pt pieces (the pieces of a puzzle contiguous and in slot order, empty slots as empty ranges), puz_piece_off int64

@@ -23,6 +23,7 @@
 #include <limits.h>
 #include <math.h>
 
+#include "mesh_common.h"
 #include "pfpp_common.h"
 
 namespace {
@@ -35,12 +36,7 @@ constexpr uint64_t EMPTY_KEY = ~0ull;
 // |x| 1e5 must stay well inside int64 before llrint (the packing refuses far smaller ranges anyway)
 constexpr double KEY_MAG_LIMIT = 4503599627370496.0;     // 2^52
 
-// status kinds (the word is (kind << 32) | index; the host decodes it in pfpp_mesh_status)
-enum : uint32_t { ST_NONFINITE = 1, ST_FACE_INDEX = 2, ST_AREA = 3, ST_KEY_MAG = 4, ST_KEY_RANGE = 5, ST_TABLE_FULL = 6 };
-
-__device__ __forceinline__ void report(uint64_t* status, uint32_t kind, int64_t index) {
-  atomicMin(reinterpret_cast<unsigned long long*>(status), (unsigned long long)(((uint64_t)kind << 32) | (uint32_t)index));
-}
+using namespace pfpp_mesh;      // the status word and sample_point (mesh_common.h)
 
 // largest p in [0, n) with off[p] <= v (off non-decreasing, off[0] <= v): the CSR row that holds element v
 __device__ __forceinline__ int64_t csr_row(const int64_t* __restrict__ off, int64_t n, int64_t v) {
@@ -128,9 +124,9 @@ __global__ __launch_bounds__(MS_BLOCK) void sample_surface_kernel(
   } else {
     const uint64_t base = (((uint64_t)data_id[part_puzzle[part]] * (uint64_t)max_parts + (uint64_t)part_slot[part]) * (uint64_t)N +
                            (uint64_t)i) * 3ull;
-    u0 = (double)(pfpp_rng_u64(seed, split, base + 0) >> 11) * 0x1.0p-53;
-    l0 = (double)(pfpp_rng_u64(seed, split, base + 1) >> 11) * 0x1.0p-53;
-    l1 = (double)(pfpp_rng_u64(seed, split, base + 2) >> 11) * 0x1.0p-53;
+    u0 = uniform53(seed, split, base + 0);
+    l0 = uniform53(seed, split, base + 1);
+    l1 = uniform53(seed, split, base + 2);
   }
   const int64_t fo = face_off[part], nf = face_off[part + 1] - fo;
   const int64_t vo = vert_off[part], nv = vert_off[part + 1] - vo;
@@ -140,33 +136,8 @@ __global__ __launch_bounds__(MS_BLOCK) void sample_surface_kernel(
     if (face_idx) face_idx[row] = -1;
     return;
   }
-  // np.searchsorted(cdf, pick, side='left'): the first j with cdf[j] >= pick, clamped to the last face
-  const double pick = u0 * total[part];
-  const double* c = cdf + fo;
-  int64_t lo = 0, hi = nf;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (c[mid] < pick) lo = mid + 1; else hi = mid;
-  }
-  const int64_t f = lo < nf ? lo : nf - 1;
+  const int64_t f = sample_point(verts + vo * 3, faces + fo * 3, nv, nf, cdf + fo, total[part], u0, l0, l1, out);
   if (face_idx) face_idx[row] = (int32_t)f;
-  // random_lengths[l0 + l1 > 1] -= 1; abs
-  if (l0 + l1 > 1.0) { l0 = l0 - 1.0; l1 = l1 - 1.0; }
-  l0 = fabs(l0); l1 = fabs(l1);
-  const int32_t* fc = faces + (fo + f) * 3;
-  const int32_t ia = fc[0], ib = fc[1], ic = fc[2];
-  if (ia < 0 || ib < 0 || ic < 0 || ia >= nv || ib >= nv || ic >= nv) {       // reported by the cdf pass
-    out[0] = out[1] = out[2] = __builtin_nan("");
-    return;
-  }
-  const double* a = verts + (vo + ia) * 3;
-  const double* b = verts + (vo + ib) * 3;
-  const double* cc = verts + (vo + ic) * 3;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double ak = a[k];
-    out[k] = ((b[k] - ak) * l0 + (cc[k] - ak) * l1) + ak;
-  }
 }
 
 // one workgroup per puzzle: scale of each of its parts (max - min over all N x 3 coordinates) and the first part of largest scale
@@ -455,6 +426,13 @@ extern "C" int pfpp_mesh_status(const uint64_t* status, pfpp_stream_t stream) {
       pfpp::set_error("%s: unsupported: puzzle %u spans 2^21 or more 1e-5 steps on an axis (the packed key range)", __func__, idx);
       return PFPP_EUNSUPPORTED;
     case ST_TABLE_FULL: pfpp::set_error("%s: unsupported: hash table of puzzle %u is full", __func__, idx); return PFPP_EUNSUPPORTED;
+    case ST_ORDER:
+      pfpp::set_error("%s: batch puzzle %u: an order entry outside its piece's samples", __func__, idx);
+      return PFPP_EINVAL;
+    case ST_COUNTS:
+      pfpp::set_error("%s: batch puzzle %u: no piece counts (a selection outside the store, more parts than max_parts, or parts x "
+                      "min_part_point > num_points)", __func__, idx);
+      return PFPP_EINVAL;
     default: pfpp::set_error("%s: unknown status word %llx", __func__, (unsigned long long)w); return PFPP_EINVAL;
   }
 }

@@ -331,6 +331,9 @@ SIGNATURES = {
     "pfpp_mesh_sample_surface": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _u64, _u32, _i64, _p, _p, _p, _p, _p],
     "pfpp_mesh_vertex_graph": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p],
     "pfpp_mesh_status": [_p, _p],
+    "pfpp_mdata_piece_counts": [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "pfpp_mdata_sample": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _u64, _u32, _p, _p, _p, _p, _p],
+    "pfpp_mdata_pose": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _u64, _u32, _p, _p, _p, _p, _p],
     # ---- matcher back end (csrc/matching.hip)
     "pfpp_match_classify_compact": [_p, _p, _p, _p, _f32, _p, _p, _i64, _i64, _p, _p, _p, _p, _p],
     "pfpp_match_gather_rows": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p],

@@ -56,6 +56,7 @@ SOURCES = {
     "matching_ptf_train.hip": ["-ffp-contract=off"],
     "pointnet_ragged_train.hip": ["-ffp-contract=off"],
     "matching_pose.hip": ["-ffp-contract=off"],
+    "matching_dataset.hip": ["-ffp-contract=off"],
 }
 # -fma-mix-insts (target feature off): without it the compiler may fold `(_Float16)(a * b + c)` into v_fma_mixlo_f16 — ONE rounding of
 # the exact value — while the `x - (float)hi` of the same hi / lo split goes through `v_cvt_f16_f32(RN32(x))`: in the rare
@@ -95,7 +96,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     objdir = CSRC / "build"
     objdir.mkdir(exist_ok=True)
     headers = [INCLUDE / "pfpp.h", CSRC / "pfpp_common.h", CSRC / "attn_choice.h", CSRC / "gemm_common.h", CSRC / "lds_asm.h", CSRC / "sa_common.h",
-               CSRC / "sinkhorn_common.h", CSRC / "attn_rows16.h", CSRC / "ptf_common.h", CSRC / "horn_common.h"]
+               CSRC / "sinkhorn_common.h", CSRC / "attn_rows16.h", CSRC / "ptf_common.h", CSRC / "horn_common.h", CSRC / "mesh_common.h"]
     # the linked library newer than every source and header: nothing to do — also where the object files did not travel (the GPU box
     # gets libpfpp_hip.so but not csrc/build/, .gpurunignore): without this a test fixture there would recompile all 25 units
     if not force and not _stale(LIB_PATH, [CSRC / src for src in SOURCES] + headers):
