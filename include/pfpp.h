@@ -860,6 +860,25 @@ int pfpp_adamw_zero(float* p, float* g, float* m, float* v, void* hi, void* lo, 
 int pfpp_adamw_guarded(float* p, float* g, float* m, float* v, void* hi, void* lo, int64_t n,
                        float lr, float beta1, float beta2, float eps, float weight_decay, float bc1,
                        float bc2, float g_scale, int zero_grad, int32_t* overflow, pfpp_stream_t stream);
+/* Adam over a list of tensors in a handful of launches (Jigsaw_matching/model/modules/matching_base_model.py:499-515: one
+ * torch.optim.Adam / AdamW over self.parameters(), which torch steps tensor by tensor or through its own multi-tensor path).  p, g, m,
+ * v: HOST arrays of n_tensors device pointers, n: host array of element counts (>= 0; a tensor with n == 0 is skipped and may have null
+ * pointers), bc1 / bc2: host arrays of the tensors' own bias corrections 1 - beta^step (torch keeps `step` per parameter; a parameter
+ * without a gradient in earlier steps has a smaller one).  Per element the update is pfpp_adamw's, bit for bit (no planes, no
+ * zero_grad, no guard): the kernel does not repeat adamw_kernel's source expressions, whose contraction the compiler chooses per
+ * kernel, but writes out the fused multiply-adds adamw_kernel<false> compiles to on gfx950 under contract(off); the GPU test that
+ * compares the two bitwise is the guard should a compiler fuse adamw_kernel differently.  g is not written.  The descriptors travel
+ * in the kernel-argument struct
+ * (<= 4 KB, no device-side table): a launch holds at most PFPP_ADAM_MULTI_MAX_TENSORS tensors and PFPP_ADAM_MULTI_MAX_BLOCKS
+ * workgroups of PFPP_ADAM_MULTI_CHUNK elements; tensors are taken in order, and one that the block capacity cuts goes on in the next
+ * launch.  Pointers need 4-byte alignment only.  Refused before any launch: n_tensors < 0, a null array, a null pointer of a
+ * non-empty tensor, n < 0, bc <= 0.  n_tensors == 0 is a no-op. */
+#define PFPP_ADAM_MULTI_MAX_TENSORS 36
+#define PFPP_ADAM_MULTI_MAX_BLOCKS 384
+#define PFPP_ADAM_MULTI_CHUNK 8192
+int pfpp_adam_multi(int64_t n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                    const float* bc1, const float* bc2, float lr, float beta1, float beta2, float eps, float weight_decay,
+                    float g_scale, pfpp_stream_t stream);
 /* the same update restricted by ROWS of a stack of embedding tables [n_tables, rows_per_table, C] (the 12 AdaLN timestep tables,
  * MyAdaLayerNorm.emb = nn.Embedding(num_embeds_ada_norm, dim), attention.py:18-25): a step touches only the rows of the batch's
  * timesteps t [n_t] (int64, device), every other row has an exactly zero gradient and its update (moment decay, weight decay, the
@@ -1434,6 +1453,16 @@ int pfpp_sinkhorn_train_bwd_seeded(const float* s, int64_t ld, int64_t n, float 
 int64_t pfpp_match_colsum_ordered_workspace(int64_t rows, int64_t cols);
 int pfpp_match_colsum_ordered(const float* x, int64_t ld, int64_t rows, int64_t cols, float* out, void* workspace, int64_t workspace_bytes,
                               pfpp_stream_t stream);
+
+/* ---- matcher, validation metrics of one puzzle (Jigsaw_matching/model/jigsaw/joint_seg_align_model.py:366-377 with utils/loss.py:26-56
+ * on the masked doubly-stochastic matrix, and :405-415, which the reference runs as per-puzzle Python over N' x N' matrices;
+ * csrc/matching_train.hip).  ds_mat [n, n] contiguous = the masked Sinkhorn output (same-piece entries exactly 0), tgt int32 [n] from
+ * pfpp_match_gt_targets (-1 = no target), col int64 [n] = the assignment's column of every row.  loss [1] (fp64) = sum_ij BCE(ds_mat_ij,
+ * [j == tgt_i]), both logs clamped at -100, exactly pfpp_sinkhorn_train_fwd's loss of the same matrix, summed in fp64 in a fixed order
+ * (two runs agree bitwise; no float atomics).  counts int64 [3] = (tp, fp, fn): tp = #{i: col_i == tgt_i}, fp = n - tp, fn = #{i: tgt_i
+ * >= 0} - tp, i.e. pred . gt, pred . (1 - gt), (1 - pred) . gt for a perm_mat with one 1 per row.  One launch; 1 <= n <= 65535. */
+int pfpp_match_val_metrics(const float* ds_mat, int64_t n, const int32_t* tgt, const int64_t* col, double* loss, int64_t* counts,
+                           pfpp_stream_t stream);
 
 /* ---- matcher middle, training: the backward of the cross-attention layer tf_cross1 (Jigsaw_matching/model/jigsaw/attention_layer.py in
  * .train() under autograd; csrc/matching_tf_train.hip).  The layer has no dropout (:15, :44, :86, :92 are commented out) and its

@@ -414,6 +414,44 @@ __global__ __launch_bounds__(64) void match_cls_fold_kernel(const double* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------------ validation metrics
+// One puzzle of validation_step in one launch of one workgroup: loss = sum_ij BCE(ds_ij, [j == tgt_i]) with skt_exp_loss_kernel's
+// terms (fp64 logs of the fp32 entry, both clamped at -100) and (tp, fp, fn) of the assignment col against tgt.  Wave w takes rows w,
+// w + 16, ...; a lane keeps one fp64 sum over all its rows and columns, the 64 lanes are folded by the butterfly, the 16 waves in
+// order by thread 0: a fixed order, two runs agree bitwise.  An entry that is exactly 0 off the target column adds log(1) = 0 and
+// is skipped: in the masked matrix those are the same-piece blocks.
+constexpr int VM_WAVES = 16;
+__global__ __launch_bounds__(64 * VM_WAVES) void match_val_metrics_kernel(const float* __restrict__ ds, int n, const int32_t* __restrict__ tgt,
+                                                                         const int64_t* __restrict__ col, double* __restrict__ loss,
+                                                                         int64_t* __restrict__ counts) {
+  __shared__ double sl[VM_WAVES];
+  __shared__ int stp[VM_WAVES], sgt[VM_WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double acc = 0.0;
+  int tp = 0, gt = 0;
+  for (int i = w; i < n; i += VM_WAVES) {
+    const float* row = ds + (int64_t)i * n;
+    const int t = tgt[i];
+    if (lane == 0) { tp += t >= 0 && col[i] == (int64_t)t; gt += t >= 0; }
+    for (int j = lane; j < n; j += 64) {
+      const float p = row[j];
+      if (j != t && p == 0.0f) continue;
+      const double q = j == t ? (double)p : fmax(1.0 - (double)p, 0.0);
+      acc -= fmax(log(q), -100.0);
+    }
+  }
+  acc = wave_sum_f64(acc);
+  if (lane == 0) { sl[w] = acc; stp[w] = tp; sgt[w] = gt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    int64_t ntp = 0, ngt = 0;
+    for (int k = 0; k < VM_WAVES; ++k) { tot += sl[k]; ntp += stp[k]; ngt += sgt[k]; }
+    loss[0] = tot;
+    counts[0] = ntp; counts[1] = (int64_t)n - ntp; counts[2] = ngt - ntp;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ raw rows
 // out[r] = feats[idx[r]], a zero row where idx[r] is outside [0, N): 32 lanes x float4 = one 128-wide row
 __global__ __launch_bounds__(256) void match_gather_raw_kernel(const float* __restrict__ feats, const int64_t* __restrict__ idx, int64_t N,
@@ -664,5 +702,14 @@ extern "C" int pfpp_match_scatter_raw(const float* in, const int64_t* idx, int64
   if (R == 0) return PFPP_OK;
   hipLaunchKernelGGL(match_scatter_raw_kernel, dim3((unsigned)((R + 7) / 8)), dim3(256), 0, pfpp::as_stream(stream), in, idx, N, R, accumulate,
                      out);
+  return pfpp::check_launch(__func__);
+}
+
+extern "C" int pfpp_match_val_metrics(const float* ds_mat, int64_t n, const int32_t* tgt, const int64_t* col, double* loss, int64_t* counts,
+                                      pfpp_stream_t stream) {
+  PFPP_REQUIRE(ds_mat && tgt && col && loss && counts, "null pointer");
+  PFPP_REQUIRE(n >= 1, "bad sizes");
+  PFPP_SUPPORTED(n <= 65535, "more than 65535 critical points in one puzzle");
+  hipLaunchKernelGGL(match_val_metrics_kernel, dim3(1), dim3(64 * VM_WAVES), 0, pfpp::as_stream(stream), ds_mat, (int)n, tgt, col, loss, counts);
   return pfpp::check_launch(__func__);
 }

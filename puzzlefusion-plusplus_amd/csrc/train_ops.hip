@@ -604,6 +604,78 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   }
 }
 
+// Adam over a list of tensors (pfpp_adam_multi): the tensors' descriptors and the launch's (tensor, chunk) block map travel in the
+// kernel-argument struct, so a step over many small tensors is a handful of launches and no device-side table exists that could be
+// stale (the engines allocate new gradient tensors every step).  Per element the arithmetic is adamw_kernel<false>'s
+// (adam_multi_element below), without planes, zero_grad and guard: the results are bit for bit pfpp_adamw's.  The pointers are only
+// 4-byte aligned (parameters can be views), so every access is one dword; a wave's access is 256 contiguous bytes.
+constexpr int AM_TENSORS = PFPP_ADAM_MULTI_MAX_TENSORS, AM_BLOCKS = PFPP_ADAM_MULTI_MAX_BLOCKS, AM_CHUNK = PFPP_ADAM_MULTI_CHUNK;
+struct AdamMultiArgs {
+  float* p[AM_TENSORS];
+  const float* g[AM_TENSORS];
+  float* m[AM_TENSORS];
+  float* v[AM_TENSORS];
+  int64_t n[AM_TENSORS];
+  float step_size[AM_TENSORS];          // lr / bc1 of the tensor's own step count
+  float inv_sqrt_bc2[AM_TENSORS];
+  int32_t blk_chunk[AM_BLOCKS];         // workgroup b works on elements [blk_chunk[b] * AM_CHUNK, + AM_CHUNK) of tensor blk_tensor[b]
+  uint8_t blk_tensor[AM_BLOCKS];
+  float decay, w1, beta2, w2, eps, g_scale;
+};
+static_assert(sizeof(AdamMultiArgs) <= 4096, "the kernel-argument segment of pfpp_adam_multi is kept within 4 KB");
+static_assert(AM_TENSORS <= 256 && AM_CHUNK % (256 * 4) == 0, "blk_tensor is a byte; a chunk is whole passes of 256 threads x 4");
+
+// adamw_kernel's update of one element with its fused multiply-adds written out.  That kernel's source leaves the contraction
+// of `v * beta2 + w2 * (g * g)` (two products and a sum) and of the other three sums to the compiler, which fuses within one
+// kernel as its instruction selection happens to fall: the same source expression in this kernel came out as fma(beta2, v, w2 g^2)
+// where adamw_kernel has fma(w2, g^2, beta2 v), one rounding apart.  The forms below are adamw_kernel<false>'s as compiled for
+// gfx950, pinned: every product that is rounded on its own there is a statement of its own here, under contract(off).
+__device__ __forceinline__ float adam_multi_element(float p, float g, float& m, float& v, float decay, float w1, float beta2, float w2,
+                                                    float eps, float step_size, float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  const float gg = g * g;
+  const float vb = v * beta2;
+  v = __builtin_fmaf(w2, gg, vb);
+  const float d = g - m;
+  m = __builtin_fmaf(w1, d, m);
+  const float denom = __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+  const float q = m / denom;
+  const float upd = step_size * q;
+  return __builtin_fmaf(decay, p, -upd);
+}
+
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamMultiArgs a) {
+  const int t = a.blk_tensor[blockIdx.x];
+  float* __restrict__ p = a.p[t];
+  const float* __restrict__ g = a.g[t];
+  float* __restrict__ m = a.m[t];
+  float* __restrict__ v = a.v[t];
+  const int64_t n = a.n[t];
+  const float step_size = a.step_size[t], inv_sqrt_bc2 = a.inv_sqrt_bc2[t];
+  const float decay = a.decay, w1 = a.w1, beta2 = a.beta2, w2 = a.w2, eps = a.eps, g_scale = a.g_scale;
+  const int64_t first = (int64_t)a.blk_chunk[blockIdx.x] * AM_CHUNK;
+  const int64_t base = first + threadIdx.x;
+  const int passes = (int)((min(n - first, (int64_t)AM_CHUNK) + 256 * 4 - 1) / (256 * 4));     // the last chunk of a tensor is short
+#pragma unroll 1
+  for (int it = 0; it < passes; ++it) {
+    float gr[4], pp[4], mm[4], vv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                      // four independent dwords per array in flight
+      const int64_t i = base + (int64_t)(it * 4 + k) * 256;
+      const bool in = i < n;
+      gr[k] = in ? g[i] * g_scale : 0.0f;
+      pp[k] = in ? p[i] : 0.0f; mm[k] = in ? m[i] : 0.0f; vv[k] = in ? v[i] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t i = base + (int64_t)(it * 4 + k) * 256;
+      if (i >= n) continue;
+      p[i] = adam_multi_element(pp[k], gr[k], mm[k], vv[k], decay, w1, beta2, w2, eps, step_size, inv_sqrt_bc2);
+      m[i] = mm[k]; v[i] = vv[k];
+    }
+  }
+}
+
 // AdamW over a stack of embedding tables restricted by rows (see pfpp_adamw_rows): MODE 0 = one thread per element of the stack, rows
 // listed in t skipped (a 3,072-bit row mask built in LDS per workgroup); MODE 1 = one thread per element of the listed rows, a row
 // listed twice is taken by its first occurrence only; MODE 2 = one thread per element of the stack, rows whose bit is CLEAR in the bitmap
@@ -1059,5 +1131,43 @@ extern "C" int pfpp_adamw_guarded(float* p, float* g, float* m, float* v, void* 
     hipLaunchKernelGGL(adamw_kernel<false>, grid, dim3(256), 0, st, p, g, m, v, (_Float16*)hi, (_Float16*)lo, n,
                        1.0f - lr * weight_decay, 1.0f - beta1, beta2, 1.0f - beta2, eps, lr / bc1, 1.0f / sqrtf(bc2), g_scale,
                        zero_grad ? 1 : 0, (int*)nullptr);
+  return pfpp::check_launch(__func__);
+}
+
+extern "C" int pfpp_adam_multi(int64_t n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                               const float* bc1, const float* bc2, float lr, float beta1, float beta2, float eps, float weight_decay,
+                               float g_scale, pfpp_stream_t stream) {
+  PFPP_REQUIRE(n_tensors >= 0, "negative tensor count");
+  if (n_tensors == 0) return PFPP_OK;
+  PFPP_REQUIRE(p && g && m && v && n && bc1 && bc2, "null array");
+  for (int64_t t = 0; t < n_tensors; ++t) {            // every refusal comes before the first launch
+    PFPP_REQUIRE(n[t] >= 0, "negative element count");
+    PFPP_REQUIRE(n[t] == 0 || (p[t] && g[t] && m[t] && v[t]), "null pointer in the list");
+    PFPP_REQUIRE(bc1[t] > 0.0f && bc2[t] > 0.0f, "bias corrections must be positive");
+    PFPP_SUPPORTED(n[t] <= (int64_t)AM_CHUNK * 0x7fffffff, "tensor too long for a 32-bit chunk index");
+  }
+  hipStream_t st = pfpp::as_stream(stream);
+  AdamMultiArgs a;
+  a.decay = 1.0f - lr * weight_decay; a.w1 = 1.0f - beta1; a.beta2 = beta2; a.w2 = 1.0f - beta2; a.eps = eps; a.g_scale = g_scale;
+  int nt = 0, nb = 0;                                   // tensors and blocks in the launch being filled
+  auto flush = [&]() {
+    if (nb > 0) hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)nb), dim3(256), 0, st, a);
+    nt = nb = 0;
+  };
+  // the chunking pfpp_hip.matching_fit.plan_adam_multi restates: tensors in order, empty ones skipped, a launch is closed when it
+  // holds AM_TENSORS tensors or AM_BLOCKS blocks; a tensor cut by the block capacity goes on in the next launch
+  for (int64_t t = 0; t < n_tensors; ++t) {
+    const int64_t chunks = (n[t] + AM_CHUNK - 1) / AM_CHUNK;
+    int64_t c = 0;
+    while (c < chunks) {
+      if (nt == AM_TENSORS || nb == AM_BLOCKS) flush();
+      a.p[nt] = p[t]; a.g[nt] = g[t]; a.m[nt] = m[t]; a.v[nt] = v[t]; a.n[nt] = n[t];
+      a.step_size[nt] = lr / bc1[t]; a.inv_sqrt_bc2[nt] = 1.0f / sqrtf(bc2[t]);
+      const int64_t take = chunks - c < AM_BLOCKS - nb ? chunks - c : AM_BLOCKS - nb;
+      for (int64_t k = 0; k < take; ++k) { a.blk_chunk[nb + k] = (int32_t)(c + k); a.blk_tensor[nb + k] = (uint8_t)nt; }
+      nb += (int)take; c += take; ++nt;
+    }
+  }
+  flush();
   return pfpp::check_launch(__func__);
 }

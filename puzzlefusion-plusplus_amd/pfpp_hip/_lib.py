@@ -364,6 +364,9 @@ SIGNATURES = {
     "pfpp_rigid_grad": [_i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
     "pfpp_sinkhorn_train_bwd_seeded": [_p, _i64, _i64, _f32, _i64, _p, _p, _p, _f32, _p, _i64, _p, _i64, _p],
     "pfpp_match_colsum_ordered": [_p, _i64, _i64, _i64, _p, _p, _i64, _p],
+    # ---- matcher, fitting: multi-tensor Adam (csrc/train_ops.hip) and the validation metrics (csrc/matching_train.hip)
+    "pfpp_adam_multi": [_i64, _p, _p, _p, _p, _p, _p, _p, _f32, _f32, _f32, _f32, _f32, _f32, _p],
+    "pfpp_match_val_metrics": [_p, _i64, _p, _p, _p, _p, _p],
     # ---- matcher middle, training (csrc/matching_tf_train.hip)
     "pfpp_attn_rows16_train": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
     "pfpp_attn_rows16_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],

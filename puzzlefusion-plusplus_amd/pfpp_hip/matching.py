@@ -469,7 +469,8 @@ class DescriptorNetwork(nn.Module):
 
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError("DescriptorNetwork runs in eval mode only: matcher training is not built")
+            raise NotImplementedError("DescriptorNetwork runs in eval mode only: matcher training goes through pfpp_hip.matching_fit (MatcherTrainer / fit, "
+                                      "python -m pfpp_hip.train_matching), whose engines step this module's parameters")
         return super().train(False)
 
     @classmethod
