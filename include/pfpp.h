@@ -1464,6 +1464,29 @@ int pfpp_match_colsum_ordered(const float* x, int64_t ld, int64_t rows, int64_t 
 int pfpp_match_val_metrics(const float* ds_mat, int64_t n, const int32_t* tgt, const int64_t* col, double* loss, int64_t* counts,
                            pfpp_stream_t stream);
 
+/* ---- matcher, assignment: the optimal assignment of a batch of puzzles on the device (hungarian / _hung_kernel,
+ * Jigsaw_matching/utils/linear_solvers.py:279-340, which hands every puzzle's matrix to scipy.optimize.linear_sum_assignment on the
+ * host, one after the other; csrc/matching_assign.hip).  For each puzzle b: c[b] = a device pointer to its float32 [n_b, n_b]
+ * contiguous matrix (the masked Sinkhorn output); the result maximises sum_i c[i, col_i] over permutations.  c, n and max_steps are
+ * HOST arrays of length B; the outputs are device arrays in which puzzle b owns the n_b entries behind those of the puzzles before
+ * it (col int64, u and v fp64: the duals of cost = -(double)c) and entry b (status int32, steps and augmentations int64).
+ * The algorithm, in fp64 additions, subtractions and comparisons only (bit for bit pfpp_hip.matching_assign.assign_reference):
+ * u_i = min_j cost_ij, v = 0; column j goes to the lowest row whose lowest minimal column it is; the rows left free are taken in
+ * ascending order, each by one shortest augmenting path whose step relaxes the unscanned columns from the current row,
+ * r = ((minv + cost_ij) - u_i) - v_j, and scans the unscanned column with the smallest (dist, assigned, index), an unassigned one
+ * being the sink; then u and v of the scanned set move by minv - dist_j as in scipy's solver.  One workgroup per puzzle, all
+ * puzzles of a launch concurrently, PFPP_MATCH_ASSIGN_MAX_PUZZLES to a launch (their descriptors travel in the kernel arguments).
+ * max_steps[b] bounds the search steps of puzzle b over all its searches: when it is used up status[b] = 1 and col of that
+ * puzzle is unspecified (status 0 = solved; 2 = a search found no column within finite reach, i.e. the matrix holds NaN or infinite
+ * entries, col unspecified as well); no loop of the kernels is unbounded.  workspace: pfpp_match_assign_workspace(B, n)
+ * bytes (-1 for B < 1, a null n or an n_b outside 1..PFPP_MATCH_ASSIGN_MAX_N), 4-byte aligned.  Two runs agree bitwise.        */
+#define PFPP_MATCH_ASSIGN_MAX_N 8192
+#define PFPP_MATCH_ASSIGN_MAX_PUZZLES 64
+int64_t pfpp_match_assign_workspace(int64_t B, const int64_t* n);
+int pfpp_match_assign(int64_t B, const float* const* c, const int64_t* n, const int64_t* max_steps, int64_t* col, double* u, double* v,
+                      int32_t* status, int64_t* steps, int64_t* augmentations, void* workspace, int64_t workspace_bytes,
+                      pfpp_stream_t stream);
+
 /* ---- matcher middle, training: the backward of the cross-attention layer tf_cross1 (Jigsaw_matching/model/jigsaw/attention_layer.py in
  * .train() under autograd; csrc/matching_tf_train.hip).  The layer has no dropout (:15, :44, :86, :92 are commented out) and its
  * norms are nn.LayerNorm: its training-time forward is the eval forward.  The linear layers' gradients go through pfpp_gemm in its

@@ -35,6 +35,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--gemm", choices=("f32", "f16x3"), default="f32")
     ap.add_argument("--shape-cd-index", choices=("reference", "corrected"), default="reference")
+    ap.add_argument("--assignment", choices=("host", "device"), default="host",
+                    help="the optimal assignment: scipy on the host, or the batched exact solver on the GPU (pfpp_hip.matching_assign)")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be at least 1")
@@ -60,7 +62,7 @@ def main(argv: Optional[List[str]] = None) -> int:
 
     ev = MatchingEvaluator(n_hyp=args.n_hyp, seed=args.seed, refine=args.refine, shape_cd_index=args.shape_cd_index)
     for ids, items, n_pcs, valids, out in head_batches(source, args.points is not None, args.checkpoint, args.gemm, args.seed, todo, args.batch_size,
-                                                       extra=POSE_KEYS):
+                                                       extra=POSE_KEYS, solver=args.assignment):
         P = n_pcs.shape[1]
         nc = out.n_critical_pcs.cpu().numpy()
         same = len({x["part_pcs"].shape[0] for x in items}) == 1

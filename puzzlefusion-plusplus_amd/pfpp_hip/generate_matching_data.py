@@ -52,9 +52,11 @@ def load_features(features: str, data_id: int, points: bool = False, extra=()):
     return x
 
 
-def head_batches(source: str, points: bool, checkpoint: str, gemm: str, seed: int, todo, batch_size: int, extra=(), dense_perm: bool = False):
+def head_batches(source: str, points: bool, checkpoint: str, gemm: str, seed: int, todo, batch_size: int, extra=(), dense_perm: bool = False,
+                 solver: str = "host"):
     """the models of a checkpoint over the puzzles `todo` of a directory, batch by batch: pfpp_hip.matching.DescriptorNetwork in
     front of the head when the files hold points, the head alone when they hold descriptors
+    (solver: the head's assignment solver, "host" or "device")
     -> yields (data ids, the puzzles' files, n_pcs [b, P], part_valids [b, P], the head's output)"""
     import numpy as np
     import torch
@@ -74,7 +76,7 @@ def head_batches(source: str, points: bool, checkpoint: str, gemm: str, seed: in
                         seed=seed + i)
         else:
             feats = [torch.from_numpy(np.ascontiguousarray(x["part_feats"], dtype=np.float32)).cuda() for x in items]
-        yield ids, items, n_pcs, valids, head(feats, n_pcs, valids, dense_perm=dense_perm)
+        yield ids, items, n_pcs, valids, head(feats, n_pcs, valids, dense_perm=dense_perm, solver=solver)
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -87,6 +89,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--gemm", choices=("f32", "f16x3"), default="f32")
     ap.add_argument("--seed", type=int, default=0, help="--points: seed of the encoder's sampling starts (the reference draws them at random)")
+    ap.add_argument("--assignment", choices=("host", "device"), default="host",
+                    help="the optimal assignment: scipy on the host, or the batched exact solver on the GPU (pfpp_hip.matching_assign)")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be at least 1")
@@ -110,9 +114,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 2
     from pfpp_hip.matching import match_edges, write_matching_data
 
-    t0, n, host = time.perf_counter(), 0, 0.0
-    for ids, items, n_pcs, valids, out in head_batches(source, args.points is not None, args.checkpoint, args.gemm, args.seed, todo, args.batch_size):
+    t0, n, host, device = time.perf_counter(), 0, 0.0, 0.0
+    for ids, items, n_pcs, valids, out in head_batches(source, args.points is not None, args.checkpoint, args.gemm, args.seed, todo, args.batch_size,
+                                                       solver=args.assignment):
         host += out.timings["host_assignment_s"]
+        device += out.timings["device_assignment_s"]
         nc = out.n_critical_pcs.cpu().numpy()
         for b, (d, x) in enumerate(zip(ids, items)):
             p = x["n_pcs"].shape[0]
@@ -121,7 +127,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                                 n_pcs=x["n_pcs"], n_critical_pcs=nc[b, :p])
             n += 1
     dt = time.perf_counter() - t0
-    print(f"{n} puzzles -> {args.out} in {dt:.2f} s ({n / max(dt, 1e-9):.1f} files/s; host assignment {host:.2f} s)", flush=True)
+    print(f"{n} puzzles -> {args.out} in {dt:.2f} s ({n / max(dt, 1e-9):.1f} files/s; host assignment {host:.2f} s" +
+          (f", device assignment {device:.2f} s" if args.assignment == "device" else "") + ")", flush=True)
     return 0
 
 

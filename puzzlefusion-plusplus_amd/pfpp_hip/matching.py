@@ -4,7 +4,8 @@ The test-time path of the reference's Jigsaw_matching/model/jigsaw/joint_seg_ali
 and model/modules/matching_base_model.py:298-361, 614-640 up to the file:
 
 * MatchingHead: fracture-point classifier, critical points, affinity features, dual affinity, same-piece mask, Sinkhorn (on the
-  GPU, ragged over the puzzles of a batch) and the optimal assignment (scipy on the host, overlapped with the next puzzle's GPU work).
+  GPU, ragged over the puzzles of a batch) and the optimal assignment (scipy on the host, overlapped with the next puzzle's GPU work;
+  with solver="device" the exact batched solver of pfpp_hip/matching_assign.py instead).
 * sinkhorn / fracture_labels: the two kernels on their own.
 * match_edges: the piece-pair rule that turns the assignment into `edges` and `correspondence` (host: O(N') integer work on an
   array the host already holds for the assignment).
@@ -350,14 +351,22 @@ class MatchingHead(nn.Module):
         return ops.gemm(f, a_t, M=f.shape[0], N=h, K=h, lda=AFF_FEAT_DIM, mode=self.gemm_mode)
 
     @torch.no_grad()
-    def forward(self, part_feats, n_pcs, part_valids, *, dense_perm: bool = True, overlap: bool = True, assign: bool = True) -> HeadOutput:
-        """part_feats: float32 [B, N, 128], a list of [N_b, 128] or flat [sum N, 128]; n_pcs int [B, P]; part_valids [B, P]"""
+    def forward(self, part_feats, n_pcs, part_valids, *, dense_perm: bool = True, overlap: bool = True, assign: bool = True,
+                solver: str = "host", max_steps=None) -> HeadOutput:
+        """part_feats: float32 [B, N, 128], a list of [N_b, 128] or flat [sum N, 128]; n_pcs int [B, P]; part_valids [B, P].
+        solver: "host" = scipy on the host, overlapped with the next puzzle's GPU work; "device" = one batched launch of the exact
+        device solver over all puzzles behind their Sinkhorn (pfpp_hip.matching_assign.assign_batch; no pinned buffers, no copy stream,
+        no download of ds_mat).  max_steps: that solver's step budget (None = its default); a puzzle whose budget runs out is solved
+        on the host, with one warning."""
         import time
+        import warnings
 
         from scipy.optimize import linear_sum_assignment
 
         first = part_feats[0] if isinstance(part_feats, (list, tuple)) else part_feats
         _gpu(first, torch.float32, "part_feats")
+        if solver not in ("host", "device"):
+            raise ValueError(f"solver: expected 'host' or 'device', got {solver!r}")
         dev = first.device
         layout = make_layout(n_pcs, dev)
         feats = _flatten(part_feats, layout, PC_FEAT_DIM, "part_feats")
@@ -377,15 +386,17 @@ class MatchingHead(nn.Module):
         pa = self.primal_times_a(f) if rows[-1] else None
         ds_list: List[torch.Tensor] = []
         perm_list: List[Optional[torch.Tensor]] = [None] * B
-        copy_stream = torch.cuda.Stream(dev)
+        copy_stream = torch.cuda.Stream(dev) if solver == "host" else None
         # Two pinned buffers sized to the largest puzzle, taken in turn by the jobs SUBMITTED (n_jobs; skipped puzzles do not count).
         # Invariant: at most one job is pending, and job k is solved before job k + 1 becomes pending, so when job k + 2 takes the
         # buffer of job k that job's assignment has been read out of it.
-        n_big = max((int(rows[b + 1] - rows[b]) for b in range(B) if (nc[b] > 0).sum() >= 2), default=0) if assign else 0
+        n_big = max((int(rows[b + 1] - rows[b]) for b in range(B) if (nc[b] > 0).sum() >= 2), default=0) if assign and solver == "host" else 0
         pinned = [torch.empty(n_big * n_big, dtype=torch.float32, pin_memory=True) for _ in range(2 if n_big else 0)]
-        host_s = copy_s = 0.0
+        host_s = copy_s = device_s = 0.0
         pending = None
         n_jobs = 0
+        device_jobs: List[int] = []           # solver == "device": the puzzles behind their Sinkhorn, solved in one call after the loop
+        fallback: List[int] = []
 
         def solve(job):
             nonlocal host_s, copy_s
@@ -410,6 +421,9 @@ class MatchingHead(nn.Module):
             if not assign:
                 perm_list[b] = torch.empty(0, dtype=torch.int64)
                 continue
+            if solver == "device":
+                device_jobs.append(b)
+                continue
             n = r1 - r0
             buf = pinned[n_jobs % 2][:n * n].view(n, n)
             n_jobs += 1
@@ -428,6 +442,25 @@ class MatchingHead(nn.Module):
                 pending = job
         if pending is not None:
             solve(pending)
+        if device_jobs:
+            from .matching_assign import assign_batch
+
+            t1 = time.perf_counter()
+            res = assign_batch([ds_list[b] for b in device_jobs], max_steps=max_steps)
+            status = res.status.cpu().numpy()                 # B words: the one wait for the launch
+            device_s = time.perf_counter() - t1
+            for k, b in enumerate(device_jobs):
+                if status[k] == 0:
+                    perm_list[b] = res.col[k]
+                    continue
+                fallback.append(b)
+                t1 = time.perf_counter()
+                _, col = linear_sum_assignment(-ds_list[b].cpu().numpy())
+                host_s += time.perf_counter() - t1
+                perm_list[b] = torch.from_numpy(col.astype(np.int64))
+            if fallback:
+                warnings.warn(f"device assignment: the step budget (max_steps = {'the default' if max_steps is None else max_steps}) ran out for "
+                              f"puzzle(s) {fallback} of the batch; solved on the host instead")
         torch.cuda.current_stream(dev).synchronize()
         wall = time.perf_counter() - t0
         perms = []
@@ -444,7 +477,8 @@ class MatchingHead(nn.Module):
         sizes = layout.puz_points.tolist()
         return HeadOutput([t.reshape(-1, 1) for t in torch.split(logits, sizes)], list(torch.split(labels.to(torch.int64), sizes)),
                           list(torch.split(crit, sizes)), n_crit.reshape(B, P), ds_list, perms,
-                          {"wall_s": wall, "host_assignment_s": host_s, "wait_for_copy_s": copy_s})
+                          {"wall_s": wall, "host_assignment_s": host_s, "wait_for_copy_s": copy_s, "device_assignment_s": device_s,
+                           "fallback_puzzles": len(fallback)})
 
 
 # ------------------------------------------------------------------------------------------------------------------ the descriptor network

@@ -285,8 +285,13 @@ class MatcherValidator:
     Sinkhorn output the uniform matrix 1 / n, every target masked away.  It adds n^2 BCE(1 / n, 0) to the loss sum, n to fp and n to
     the row count (tools/make_matching_fit_goldens.py prints the reference's figures); no assignment is solved for it."""
 
-    def __init__(self, net, head, *, w_rig_loss: float = 0.0):
+    def __init__(self, net, head, *, w_rig_loss: float = 0.0, solver: str = "host", max_steps=None):
+        """solver: "host" (scipy) or "device" (pfpp_hip.matching_assign.assign_batch: one launch over the puzzles of the batch, whose
+        columns go straight into the metrics kernel; a puzzle whose step budget max_steps runs out is solved on the host)"""
+        if solver not in ("host", "device"):
+            raise ValueError(f"solver: expected 'host' or 'device', got {solver!r}")
         self.net, self.head, self.w_rig_loss = net, head, float(w_rig_loss)
+        self.solver, self.max_steps = solver, max_steps
         self.saved: dict = {}
         self.timings: dict = {}
 
@@ -335,7 +340,8 @@ class MatcherValidator:
         counts = torch.zeros((B, 3), dtype=torch.int64, device=dev)
         ds_list: List[torch.Tensor] = [torch.empty((0, 0), dtype=torch.float32, device=dev) for _ in range(B)]
         cols: List[Optional[torch.Tensor]] = [None] * B
-        host_s = 0.0
+        host_s = device_s = 0.0
+        fallback: List[int] = []
         if R:
             f, row_piece = head.affinity_features(feats, layout, crit, crit_off, R)
             pa = head.primal_times_a(f)
@@ -343,11 +349,11 @@ class MatcherValidator:
             piece_of_row = torch.bucketize(src, layout.piece_off[1:], right=True).to(torch.int32)
             tgt = gt_targets(pts, src, piece_of_row, torch.from_numpy(rows).to(dev), n_max)
             solved = [b for b in range(B) if (nc[b] > 0).sum() >= 2]
-            n_big = max((int(rows[b + 1] - rows[b]) for b in solved), default=0)
+            n_big = max((int(rows[b + 1] - rows[b]) for b in solved), default=0) if self.solver == "host" else 0
             # two pinned buffers taken in turn by the solved puzzles: at most one job is pending and job k is solved before job k + 1
             # becomes pending, so when job k + 2 takes job k's buffer that assignment has been read out of it (MatchingHead.forward)
             pinned = [torch.empty(n_big * n_big, dtype=torch.float32, pin_memory=True) for _ in range(2 if n_big else 0)]
-            copy_stream = torch.cuda.Stream(dev)
+            copy_stream = torch.cuda.Stream(dev) if self.solver == "host" else None
             pending, n_jobs = None, 0
 
             def solve(job):
@@ -371,6 +377,8 @@ class MatcherValidator:
                     continue
                 s = head.affinity(f, r0, r1, pa)
                 ds_list[b] = sinkhorn(s, row_piece[r0:r1], tau=head.tau, max_iter=head.max_iter, check_pieces=False)
+                if self.solver == "device":
+                    continue
                 buf = pinned[n_jobs % 2][:n * n].view(n, n)
                 n_jobs += 1
                 copy_stream.wait_stream(torch.cuda.current_stream(dev))
@@ -384,6 +392,27 @@ class MatcherValidator:
                 pending = (b, buf, ev)
             if pending is not None:
                 solve(pending)
+            if self.solver == "device" and solved:
+                import warnings
+
+                from .matching_assign import assign_batch
+
+                t = time.perf_counter()
+                res = assign_batch([ds_list[b] for b in solved], max_steps=self.max_steps)
+                status = res.status.cpu().numpy()                         # B words: the one wait for the launch
+                device_s = time.perf_counter() - t
+                for k, b in enumerate(solved):
+                    cols[b] = res.col[k]
+                    if status[k] != 0:
+                        fallback.append(b)
+                        t = time.perf_counter()
+                        _, col = linear_sum_assignment(-ds_list[b].cpu().numpy())
+                        host_s += time.perf_counter() - t
+                        cols[b] = torch.from_numpy(col.astype(np.int64)).to(dev)
+                    val_metrics(ds_list[b], tgt[rows[b]:rows[b + 1]], cols[b], losses[b:b + 1], counts[b])
+                if fallback:
+                    warnings.warn(f"device assignment: the step budget (max_steps = {'the default' if self.max_steps is None else self.max_steps}) "
+                                  f"ran out for puzzle(s) {fallback} of the batch; solved on the host instead")
         mat_loss = losses.sum() / R if R else torch.zeros((), dtype=torch.float64, device=dev)
         out = {"batch_size": B, "cls_loss": cls_loss[0].clone(), "mat_loss": mat_loss, "N_": torch.tensor(n_max)}
         if self.w_rig_loss > 0 and R:
@@ -399,7 +428,8 @@ class MatcherValidator:
             out["rig_loss"] = torch.zeros((), dtype=torch.float64, device=dev)
         host = torch.cat([out["cls_loss"].reshape(1), out["mat_loss"].reshape(1), c4.double(), counts.sum(0).double()]).cpu()
         torch.cuda.current_stream(dev).synchronize()
-        self.timings = {"wall_s": time.perf_counter() - t0, "host_assignment_s": host_s}
+        self.timings = {"wall_s": time.perf_counter() - t0, "host_assignment_s": host_s, "device_assignment_s": device_s,
+                        "fallback_puzzles": len(fallback)}
         tp4, fp4, tn4, fn4 = (host[2 + i].to(torch.float32) for i in range(4))
         ratio = lambda a, b: a / b if float(b) > 0 else torch.zeros((), dtype=torch.float32)
         out.update(cls_loss=host[0], mat_loss=host[1], loss=host[0] + host[1], cls_acc=ratio(tp4 + tn4, tp4 + fp4 + tn4 + fn4), cls_precision=ratio(tp4, tp4 + fp4),
@@ -434,6 +464,7 @@ def default_config() -> dict:
         "CALLBACK": {"MATCHING_TASK": ["trans"], "CHECKPOINT_MONITOR": "val/loss", "CHECKPOINT_MODE": "min"},
         "LOSS": {}, "EVAL": {}, "GPUS": [0], "PARALLEL_STRATEGY": "ddp", "FP16": False, "CUDNN": False, "WEIGHT_FILE": "", "OUTPUT_PATH": "",
         "STATISTIC_STEP": 100, "RANDOM_SEED": 42, "STATS": "",
+        "VAL_ASSIGNMENT": "host",      # not a key of the reference: the validator's assignment solver, "host" (scipy) or "device"
         "DATA": {"DATA_DIR": "../Breaking-Bad-Dataset.github.io/data/", "DATA_FN": "everyday.{}.txt", "DATA_KEYS": ("part_ids",), "SUBSET": "",
                  "CATEGORY": "", "ROT_RANGE": -1.0, "NUM_PC_POINTS": 5000, "MIN_PART_POINT": 30, "MIN_NUM_PART": 2, "MAX_NUM_PART": 20,
                  "SHUFFLE_PARTS": False, "SAMPLE_BY": "area", "LENGTH": -1, "TEST_LENGTH": -1, "OVERFIT": -1, "FRACTURE_LABEL_THRESHOLD": 0.025},
@@ -653,7 +684,7 @@ class MatcherTrainer:
         return {k: (float(v) if torch.is_tensor(v) else v) for k, v in self.head_engine.last_loss_dict.items()}
 
     def validate(self, epoch: int) -> dict:
-        validator = MatcherValidator(self.net, self.head, w_rig_loss=self.head_engine.w_rig_loss)
+        validator = MatcherValidator(self.net, self.head, w_rig_loss=self.head_engine.w_rig_loss, solver=self.cfg["VAL_ASSIGNMENT"])
         self.val_loader.set_epoch(0)                   # the same validation samples every time: the figures of two epochs compare
         outs = [validator.step(d, seed=_mix_seed(self.seed, 0, i, 2)) for i, d in enumerate(self.val_loader)]
         return MatcherValidator.epoch_end(outs)

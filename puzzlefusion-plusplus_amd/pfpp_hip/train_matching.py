@@ -1,6 +1,7 @@
 """python -m pfpp_hip.train_matching --cfg FILE [KEY VALUE ...]: the reference's Jigsaw_matching/train_matching.py on the HIP path.
 FILE is one of the reference's experiment yaml files, read over the defaults its utils/config.py, dataset_config.py and
-model_config.py set (pfpp_hip.matching_fit.default_config); KEY VALUE pairs override dotted keys as its cfg_from_list does."""
+model_config.py set (pfpp_hip.matching_fit.default_config); KEY VALUE pairs override dotted keys as its cfg_from_list does.
+One key is this tree's own: VAL_ASSIGNMENT host|device, the validation pass's assignment solver (default host)."""
 from __future__ import annotations
 
 import argparse

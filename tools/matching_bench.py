@@ -10,7 +10,16 @@ host assignment, and the wall time of the whole forward with and without overlap
 (alternating, medians of `--reps` as well).
 The comparison is the same steps in PyTorch eager fp32 on the same GPU, restated here the way the reference runs them: per-piece
 nonzero loops for the critical points, the two N' x N' mask tensors built in Python loops, s * mask + neg_mask, and the full-matrix
-Sinkhorn that rewrites log_s 20 times.  --profile runs only the HIP forward (for rocprofv3 --kernel-trace --stats)."""
+Sinkhorn that rewrites log_s 20 times.  --profile runs only the HIP forward (for rocprofv3 --kernel-trace --stats).
+
+    python tools/matching_bench.py --assignment device [--out FILE]
+
+measures the device assignment solver (pfpp_hip.matching_assign) against the host path instead: the two forwards alternate in one
+process on the same batch, and on a second, harder one in which 30 % of the critical points carry the descriptor of an unrelated
+point.  Per input: wall per batch and per puzzle of both paths (median of `--reps` after one warm-up each), the solver's launch by
+device events for the batch and for its puzzles one at a time, the host solver one puzzle at a time, steps and augmentations per
+puzzle, and microseconds per search step (a single puzzle's launch over its steps).  With --profile only the device-path forward
+runs."""
 from __future__ import annotations
 
 import argparse
@@ -155,6 +164,63 @@ def eager_stages(sd, feats, n_pcs, n_valid, dev):
             "d2h_copy": t_copy / B, "host_assignment": t_lsa / B}, ds
 
 
+def weaken(cases, pzs, share: float, seed: int):
+    """the harder input: a share of every puzzle's critical points takes the descriptor of a critical point of an unrelated puzzle"""
+    rng = np.random.default_rng(seed)
+    sym = [(p, p + 1, MATCHES) for p in range(PIECES - 1)]
+    out = []
+    for k, pz in enumerate(pzs):
+        other = cases.build_puzzle([PER_PIECE] * PIECES, sym, [], 5000 + k)
+        mine, theirs = np.nonzero(pz["critical"])[0], np.nonzero(other["critical"])[0]
+        pick = mine[rng.random(mine.size) < share]
+        x = pz["part_feats"].copy()
+        x[pick] = other["part_feats"][rng.choice(theirs, pick.size, replace=False)]
+        out.append(x)
+    return out
+
+
+def assignment_bench(head, feats, n_pcs, valids, reps: int, dev) -> dict:
+    """host and device solver on one batch, alternating"""
+    from scipy.optimize import linear_sum_assignment
+
+    from pfpp_hip.matching_assign import assign_batch
+
+    B = n_pcs.shape[0]
+    walls = {"host": [], "device": []}
+    outs = {}
+    for solver in ("host", "device") * (reps + 1):             # the first pair is the warm-up
+        t0 = time.perf_counter()
+        outs[solver] = head(feats, n_pcs, valids, dense_perm=False, solver=solver)
+        torch.cuda.synchronize()
+        walls[solver].append((time.perf_counter() - t0) * 1e3)
+    ds = outs["device"].ds_mat
+    equal_rows = [int((outs["host"].perm_mat[b] == outs["device"].perm_mat[b]).sum()) for b in range(B)]
+    weight = lambda o: [float(ds[b].double()[torch.arange(ds[b].shape[0], device=dev), o.perm_mat[b]].sum()) for b in range(B)]
+    assign_batch(ds)
+    batch_ms = statistics.median(timed(lambda: assign_batch(ds), dev)[1] for _ in range(reps))
+    res = assign_batch(ds)
+    steps, augs = res.steps.tolist(), res.augmentations.tolist()
+    single_ms, host_ms = [], []
+    for b in range(B):
+        assign_batch([ds[b]])
+        single_ms.append(statistics.median(timed(lambda: assign_batch([ds[b]]), dev)[1] for _ in range(reps)))
+        a = ds[b].cpu().numpy()
+        t0 = time.perf_counter()
+        linear_sum_assignment(-a)
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    med = lambda v: statistics.median(v[1:])
+    return {"n": [int(d.shape[0]) for d in ds], "rows_with_the_hosts_column": equal_rows, "weight_host": weight(outs["host"]),
+            "weight_device": weight(outs["device"]), "fallback_puzzles": outs["device"].timings["fallback_puzzles"],
+            "host": {"wall_ms_per_batch": med(walls["host"]), "wall_ms_per_puzzle": med(walls["host"]) / B,
+                     "solver_ms_per_puzzle_alone": statistics.median(host_ms), "solver_ms_per_puzzle_alone_max": max(host_ms)},
+            "device": {"wall_ms_per_batch": med(walls["device"]), "wall_ms_per_puzzle": med(walls["device"]) / B,
+                       "solver_ms_per_batch_by_events": batch_ms, "solver_ms_per_puzzle_alone": statistics.median(single_ms),
+                       "solver_ms_per_puzzle_alone_max": max(single_ms)},
+            "steps_per_puzzle": steps, "augmentations_per_puzzle": augs,
+            "us_per_step": statistics.median(1e3 * m / s for m, s in zip(single_ms, steps) if s > 0) if any(steps) else None,
+            "us_per_step_in_the_batch": 1e3 * batch_ms / max(steps) if any(steps) else None}
+
+
 def median_of(runs):
     return {k: statistics.median(r[k] for r in runs) for k in runs[0]}
 
@@ -166,6 +232,8 @@ def main() -> int:
     ap.add_argument("--gemm", choices=("f32", "f16x3"), default="f32")
     ap.add_argument("--skip-eager", action="store_true")
     ap.add_argument("--profile", action="store_true", help="only the HIP forward, without the assignment (kernel trace)")
+    ap.add_argument("--assignment", choices=("host", "device"), default="host", help="device: measure the device solver against the host path")
+    ap.add_argument("--out", help="--assignment device: also write the JSON line to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("matching_bench: no GPU: nothing is measured without one", file=sys.stderr)
@@ -184,6 +252,21 @@ def main() -> int:
     n_pcs = np.stack([p["n_pcs"] for p in pzs])
     valids = np.stack([p["part_valids"] for p in pzs])
     B = args.puzzles
+    if args.assignment == "device":
+        hard = torch.from_numpy(np.stack(weaken(cases, pzs, 0.3, 0))).to(dev)
+        if args.profile:
+            for x in (feats, hard) * (1 + args.reps):
+                head(x, n_pcs, valids, dense_perm=False, solver="device")
+            torch.cuda.synchronize()
+            return 0
+        line = {"bench": "matching_assign", "puzzles": B, "points": PIECES * PER_PIECE, "gemm": args.gemm, "reps": args.reps,
+                "device_name": torch.cuda.get_device_name(dev), "easy": assignment_bench(head, feats, n_pcs, valids, args.reps, dev),
+                "weak_30": assignment_bench(head, hard, n_pcs, valids, args.reps, dev)}
+        text = json.dumps(line)
+        print(text)
+        if args.out:
+            Path(args.out).write_text(text + "\n")
+        return 0
     if args.profile:
         for _ in range(1 + args.reps):
             head(feats, n_pcs, valids, assign=False)
