@@ -1361,6 +1361,34 @@ int pfpp_attn_rows16(const float* qkv, float* out, const int32_t* seq_off, const
 int pfpp_layernorm128(const float* x, const float* gamma, const float* beta, float* out, int64_t rows, int64_t C, float eps,
                       pfpp_stream_t stream);
 
+/* ---- matcher front end: DGCNN encoder in eval mode (Jigsaw_matching/model/modules/encoder/dgcnn.py:41-56, 130-213; csrc/dgcnn.hip)
+ * Layout as above: the points of all pieces flat, piece_off int64 [P + 1].  A level conv_l(get_graph_feature_dynamic(x)).max(-1) is
+ * computed without the [N, 20, 2 C_in] tensor: with conv_l.0.weight = [W_a | W_b] split along its input columns, slot j of point i has
+ * the pre-activation W_a x_j + (W_b - W_a) x_i, so uv = X [W_a ; W_b - W_a]^T [N, 2 C_out] is one pfpp_gemm, and BatchNorm (eval:
+ * a per-channel scale, shift) and LeakyReLU commute with the extremum over the slots.
+ * pfpp_dgcnn_knn (:47-48: knn(x, x, 20, batch_x, batch_x) + to_dense_batch(fill_value = N, max_num_nodes = 20)): pfpp_feat_knn's
+ * arguments, key and order for K = 20 and C = 3, 64 or 128: for every row of feats [N, C] (row stride ld floats) the min(K, n_piece)
+ * nearest rows OF ITS PIECE (the row itself included) as global indices int32 [N, K], ascending by key, ties to the lower index; the
+ * remaining slots hold N.  The key is d = 0; for c = 0 .. C - 1 in order: t = a_c - b_c; d = d + t t, in fp32 without contraction,
+ * compared as (bits of d, index).  Rows of 64 / 128 channels must be 16-byte aligned (ld % 4 == 0); rows of 3 need ld >= 3 only.
+ * max_n = the largest piece as the caller states it (more than 8192 is refused); ceil(N / 64) + P workgroups, P <= 65536.
+ * pfpp_dgcnn_edge_max (:49-56 + conv_l + .max(dim=-1), :175-189): uv [N, 2 C_out] (row stride ld; u = columns [0, C_out), v the
+ * rest), idx int32 [N, K]; per point i and channel c
+ *   z_j = u[idx[i, j], c] + v[i, c]   (one fp32 add)   for idx[i, j] in [0, N),    z_j = 0 for any other index (the padded slot:
+ *                                                       the reference multiplies both halves of that slot's feature by the mask)
+ *   e   = max_j z_j where scale[c] >= 0,  min_j z_j where scale[c] < 0      (slots in order: e = z_0; e = z_j > e ? z_j : e, resp. <)
+ *   y   = e scale[c] + shift[c]   (one fp32 multiply, then one fp32 add; not fused)
+ *   out[i ldo + c] = y > 0 ? y : y slope.
+ * out points at the first column to write of a buffer with row stride ldo (x1 .. x4 land in the [N, 512] operand of conv5).
+ * C_out = 64, 128 or 256, K = 20; ld, ldo multiples of 4 and every pointer 16-byte aligned.
+ * pfpp_leaky_relu (nn.LeakyReLU(negative_slope) of conv5, :158-160): x[r ld + c] = x > 0 ? x : x slope in place over [rows, C];
+ * C and ld multiples of 4, x 16-byte aligned.                                                                                    */
+int pfpp_dgcnn_knn(const float* feats, int64_t ld, const int64_t* piece_off, int64_t P, int64_t N, int64_t C, int64_t K, int64_t max_n,
+                   int32_t* idx, pfpp_stream_t stream);
+int pfpp_dgcnn_edge_max(const float* uv, int64_t ld, const int32_t* idx, const float* scale, const float* shift, float slope, int64_t N,
+                        int64_t C_out, int64_t K, float* out, int64_t ldo, pfpp_stream_t stream);
+int pfpp_leaky_relu(float* x, int64_t rows, int64_t C, int64_t ld, float slope, pfpp_stream_t stream);
+
 /* ---- matcher head, training behind part_feats (Jigsaw_matching/model/jigsaw/joint_seg_align_model.py in .train(); csrc/matching_train.hip)
  * Train-mode BatchNorm + ReLU, the linear layers, the affinity products and Adam go through pfpp_bn_stats / pfpp_bn_apply /
  * pfpp_bn_relu_bwd, pfpp_gemm / pfpp_gemm_grad and pfpp_adamw; these entries are the rest of the step.

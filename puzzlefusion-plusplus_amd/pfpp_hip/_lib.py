@@ -349,6 +349,10 @@ SIGNATURES = {
     "pfpp_ptf_aggregate": [_p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p],
     "pfpp_attn_rows16": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
     "pfpp_layernorm128": [_p, _p, _p, _p, _i64, _i64, _f32, _p],
+    # ---- matcher front end: DGCNN encoder in eval mode (csrc/dgcnn.hip)
+    "pfpp_dgcnn_knn": [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _p],
+    "pfpp_dgcnn_edge_max": [_p, _i64, _p, _p, _p, _f32, _i64, _i64, _i64, _p, _i64, _p],
+    "pfpp_leaky_relu": [_p, _i64, _i64, _i64, _f32, _p],
     # ---- matcher head, training (csrc/matching_train.hip)
     "pfpp_sinkhorn_train_fwd": [_p, _i64, _i64, _f32, _i64, _p, _p, _p, _p, _p, _p, _i64, _p],
     "pfpp_sinkhorn_train_bwd": [_p, _i64, _i64, _f32, _i64, _p, _p, _p, _f32, _p, _i64, _p, _i64, _p],

@@ -239,17 +239,37 @@ def load_checkpoint_state_dict(path: str) -> dict:
     containers loads with weights_only=True.  A real Jigsaw checkpoint also carries `hyper_parameters` with an EasyDict, which that
     mode refuses: such a file is unpickled in full (like the other Lightning files of this tree, pfpp_hip/launch.py), with classes
     that are not installed here replaced by a placeholder, and only the state_dict is kept."""
+    return _state_dict_of(_read_checkpoint(path), path)
+
+
+def _read_checkpoint(path: str):
     try:
-        ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        return torch.load(path, map_location="cpu", weights_only=True)
     except pickle.UnpicklingError:
         try:
-            ckpt = torch.load(path, map_location="cpu", weights_only=False, pickle_module=_tolerant_pickle)
+            return torch.load(path, map_location="cpu", weights_only=False, pickle_module=_tolerant_pickle)
         except Exception as e:
             raise RuntimeError(f"{path}: not a checkpoint this loader can read ({type(e).__name__}: {e})") from e
+
+
+def _state_dict_of(ckpt, path: str) -> dict:
     sd = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
     if not isinstance(sd, dict) or not all(torch.is_tensor(v) for v in sd.values()):
         raise RuntimeError(f"{path}: no state_dict of tensors found (top-level keys: {list(ckpt)[:8] if isinstance(ckpt, dict) else type(ckpt).__name__})")
     return sd
+
+
+def checkpoint_encoder_arch(ckpt, sd: dict) -> str:
+    """which encoder a matcher checkpoint was trained with: MODEL.ENCODER of its `hyper_parameters` (directly, or under `cfg` as
+    Lightning's save_hyperparameters() files it: matching_base_model.py:19-22) when the file has it and it is a string; otherwise
+    "dgcnn.dynamic" when the state_dict holds encoder.conv5.0.weight, which only that family has, and the default encoder when not"""
+    hp = ckpt.get("hyper_parameters") if isinstance(ckpt, dict) and "state_dict" in ckpt else None
+    for cfg in (hp, hp.get("cfg") if isinstance(hp, dict) else None):
+        model = cfg.get("MODEL") if isinstance(cfg, dict) else None
+        arch = model.get("ENCODER") if isinstance(model, dict) else None
+        if isinstance(arch, str):
+            return arch
+    return "dgcnn.dynamic" if "encoder.conv5.0.weight" in sd else DEFAULT_ENCODER
 
 
 class _AffinityDual(nn.Module):
@@ -482,21 +502,48 @@ class MatchingHead(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the descriptor network
-from .matching_encoder import PointNet2PTMSGDynamic                          # noqa: E402  (the matcher's modules are re-exported here)
+from .matching_dgcnn import DGCNN, DGCNNDynamic                              # noqa: E402  (the matcher's modules are re-exported here)
+from .matching_encoder import PointNet2PTMSGDynamic                          # noqa: E402
 from .matching_transformer import CrossAttentionLayer, PointTransformerLayer  # noqa: E402
 
 DESCRIPTOR_PREFIXES = ("encoder.", "tf_self1.", "tf_cross1.")
+DEFAULT_ENCODER = "pointnet2_pt.msg.dynamic"
+
+
+def build_encoder(arch: str, feat_dim: int, global_feat: bool = False, in_feat_dim: int = 3, gemm_mode: str = "f32") -> nn.Module:
+    """build_encoder of the reference (model/modules/encoder/__init__.py:1-39) for its arch strings ('xxx.xxx.x', any case):
+    'pointnet2_pt.msg.dynamic' -> PointNet2PTMSGDynamic(in_feat_dim, feat_dim), 'dgcnn.dynamic' -> DGCNNDynamic(feat_dim, global_feat,
+    in_feat_dim).  The dense families ('pointnet2_pt.msg', 'dgcnn'), global_feat=True and every other string raise NotImplementedError."""
+    if not isinstance(arch, str):
+        raise TypeError(f"arch: expected a string such as {DEFAULT_ENCODER!r}, got {type(arch).__name__}")
+    archs = arch.lower().split(".")
+    if "pointnet2_pt" in archs:
+        if global_feat:
+            raise NotImplementedError(f"{arch}: the point-wise PointNet++ encoder has no global feature (the reference asserts the same)")
+        if "msg" not in archs:
+            raise NotImplementedError(f"{arch} not supported")
+        if "dynamic" not in archs:
+            raise NotImplementedError(f"{arch}: the dense PointNet2PTMSG is not built, only 'pointnet2_pt.msg.dynamic'")
+        if isinstance(feat_dim, (list, tuple)):
+            in_feat_dim, feat_dim = feat_dim
+        return PointNet2PTMSGDynamic(in_feat_dim, feat_dim, gemm_mode=gemm_mode)
+    if "dgcnn" in archs:
+        if "dynamic" not in archs:
+            return DGCNN(feat_dim, global_feat)                              # raises: the dense DGCNN is not built
+        return DGCNNDynamic(feat_dim, global_feat, in_feat_dim, gemm_mode=gemm_mode)
+    raise NotImplementedError(f"{arch} is not supported")
 
 
 class DescriptorNetwork(nn.Module):
-    """encoder, tf_self1 and tf_cross1 of JointSegmentationAlignmentModel (joint_seg_align_model.py:38-50, 146-162) with the reference's
-    parameter names: the points of several puzzles -> flat per-point descriptors [sum N, 128] in the layout MatchingHead.forward
-    takes.  Everything between the upload of the points and the descriptors runs on the device; the piece lengths are host data."""
+    """encoder, tf_self1 and tf_cross1 of JointSegmentationAlignmentModel (joint_seg_align_model.py:38-50, 56-64, 146-162) with the
+    reference's parameter names: the points of several puzzles -> flat per-point descriptors [sum N, 128] in the layout
+    MatchingHead.forward takes.  encoder: the reference's MODEL.ENCODER string, "pointnet2_pt.msg.dynamic" (the default) or
+    "dgcnn.dynamic".  Everything between the upload of the points and the descriptors runs on the device; the piece lengths are host data."""
 
-    def __init__(self, gemm_mode: str = "f32"):
+    def __init__(self, gemm_mode: str = "f32", encoder: str = DEFAULT_ENCODER):
         super().__init__()
         self.gemm_mode = gemm_mode
-        self.encoder = PointNet2PTMSGDynamic(3, PC_FEAT_DIM, gemm_mode=gemm_mode)
+        self.encoder = build_encoder(encoder, PC_FEAT_DIM, global_feat=False, in_feat_dim=3, gemm_mode=gemm_mode)
         self.tf_self1 = PointTransformerLayer(PC_FEAT_DIM, PC_FEAT_DIM, n_heads=8, nsampmle=16, gemm_mode=gemm_mode)
         self.tf_cross1 = CrossAttentionLayer(PC_FEAT_DIM, 8, gemm_mode=gemm_mode)
         super().train(False)
@@ -509,8 +556,11 @@ class DescriptorNetwork(nn.Module):
 
     @classmethod
     def from_checkpoint(cls, path: str, **kw) -> "DescriptorNetwork":
-        """the `encoder.*`, `tf_self1.*` and `tf_cross1.*` entries of a Jigsaw checkpoint (strict); the rest is ignored"""
-        sd = load_checkpoint_state_dict(path)
+        """the `encoder.*`, `tf_self1.*` and `tf_cross1.*` entries of a Jigsaw checkpoint (strict); the rest is ignored.  The encoder
+        family is the file's own (checkpoint_encoder_arch) unless `encoder=` names one."""
+        ckpt = _read_checkpoint(path)
+        sd = _state_dict_of(ckpt, path)
+        kw.setdefault("encoder", checkpoint_encoder_arch(ckpt, sd))
         net = cls(**kw)
         net.load_state_dict({k: v for k, v in sd.items() if k.startswith(DESCRIPTOR_PREFIXES)}, strict=True)
         return net
@@ -531,6 +581,9 @@ class DescriptorNetwork(nn.Module):
                 raise ValueError(f"puzzle {b}: its {n_valid[b]} valid pieces must be the first slots and hold at least one point each")
         lengths = layout.n_pcs.reshape(-1)
         lengths = lengths[lengths > 0]                    # get_batch_length_from_part_points: the valid pieces of all puzzles in order
-        feats = self.encoder(pts, lengths, start=start, seed=seed)
+        if isinstance(self.encoder, DGCNNDynamic):        # no sampling in this family: start / seed have nothing to act on
+            feats = self.encoder(pts, lengths)
+        else:
+            feats = self.encoder(pts, lengths, start=start, seed=seed)
         feats = self.tf_self1(pts, feats, lengths)
         return self.tf_cross1(feats, layout.puz_points)

@@ -471,10 +471,13 @@ class DescriptorTrainEngine:
     torch expression) and .backward() fill the .grad of every parameter; optimizer_step() steps the three engines."""
 
     def __init__(self, net):
-        from .matching import DescriptorNetwork
+        from .matching import DescriptorNetwork, DGCNNDynamic
 
         if not isinstance(net, DescriptorNetwork):
             raise TypeError("DescriptorTrainEngine: expected a DescriptorNetwork")
+        if isinstance(net.encoder, DGCNNDynamic):
+            raise NotImplementedError("a DescriptorNetwork with a DGCNN encoder: its forward in eval mode exists (pfpp_hip.matching_dgcnn), its "
+                                      "training step (train-mode BatchNorm over all N x 20 rows and the backward) does not")
         if net.gemm_mode != "f32":
             raise NotImplementedError("matcher training runs in the exact-fp32 GEMM mode only")
         self.net = net

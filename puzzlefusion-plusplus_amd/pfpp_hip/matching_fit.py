@@ -639,6 +639,9 @@ class MatcherTrainer:
         if len(cfg["GPUS"]) != 1:
             raise NotImplementedError(f"GPUS {cfg['GPUS']}: the matcher's fit loop runs on one GPU")
         T, M = cfg["TRAIN"], cfg["MODEL"]
+        if "dgcnn" in str(M["ENCODER"]).lower().split("."):
+            raise NotImplementedError(f"MODEL.ENCODER {M['ENCODER']!r}: the DGCNN encoder's forward in eval mode exists (generate_matching_data / "
+                                      "evaluate_matching read such a checkpoint), its training step does not")
         if M["ENCODER"] != "pointnet2_pt.msg.dynamic" or M["PC_CLS_METHOD"].lower() != "binary" or M["AFFINITY"].lower() != "aff_dual":
             raise NotImplementedError("only the reference's released configuration (PointNet++ encoder, binary classifier, dual affinity) is built")
         cosine_warmup_lr(0, T["NUM_EPOCHS"], T["LR"], T["LR_DECAY"], T["WARMUP_RATIO"], T["LR_SCHEDULER"])       # refuses an unknown scheduler now
