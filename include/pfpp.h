@@ -1389,6 +1389,46 @@ int pfpp_dgcnn_edge_max(const float* uv, int64_t ld, const int32_t* idx, const f
                         int64_t C_out, int64_t K, float* out, int64_t ldo, pfpp_stream_t stream);
 int pfpp_leaky_relu(float* x, int64_t rows, int64_t C, int64_t ld, float slope, pfpp_stream_t stream);
 
+/* ---- matcher front end, training: the DGCNN encoder in .train() under autograd (dgcnn.py:41-56, 130-213; csrc/dgcnn_train.hip) in the
+ * decomposed form above.  In train mode the BatchNorm of a level (nn.BatchNorm2d over [1, C, N, 20], :141-155) normalises with the
+ * statistics of ALL R = 20 N slot rows of the call, padded all-zero rows included; z_ij = u[idx_ij] + v[i] is never stored.
+ * C_out = 64, 128 or 256, K = 20, rows of ld floats (ld % 4 == 0), pointers 16-byte aligned (winner: 4-byte).  workspace:
+ * PFPP_DGCNN_TRAIN_WS_DOUBLES doubles whatever the sizes are.  No atomics: two runs agree bitwise.
+ * pfpp_dgcnn_edge_stats (conv_l = Conv2d + BatchNorm2d in .train() + the max over the slots, :141-155, :189-203): one gather pass over u;
+ *   e[i C + c] = max_j z_ij where gamma[c] >= 0, min_j z_ij where gamma[c] < 0, by comparisons in slot order (the first slot wins a
+ *   tie); winner[i C + c] = that slot (0 .. 19, a padded slot included); the sums of z and z^2 over all 20 N rows as fp64 partials per
+ *   workgroup (a workgroup takes ceil(N / G) consecutive points), folded in a fixed order and left at workspace[PFPP_DGCNN_TRAIN_MAX_WG *
+ *   512 ..] as sum z [C] | sum z^2 [C]; coef [4 C] = a | b | mean | rstd with rstd = 1 / sqrt(var + eps) (biased variance), a = gamma
+ *   rstd, b = beta - mean a; running_mean / running_var (optional, together) move by `momentum` with the unbiased variance.  N >= 1.
+ * pfpp_dgcnn_bn_leaky_apply (BatchNorm + nn.LeakyReLU, :141-160): out[r ldo + c] = t > 0 ? t : t slope with t = y a + b as one fp32
+ *   multiply and one fp32 add, not fused; coef as above (or pfpp_ragged_bn_stats' for conv5, :158-160).  C % 4 == 0, C <= 1024.
+ * pfpp_dgcnn_bn_leaky_bwd (autograd of the same): g = g1 + g2 (g2 optional), h[r C + c] = y a + b > 0 ? g : g slope (the forward's
+ *   operations), dbeta = sum_r h, dgamma = sum_r h (y - mean) rstd as fp64 partials folded in a fixed order, means [2 C] = dbeta /
+ *   count | dgamma / count.  dy (optional, may alias h): dy = a ((h - m1) - (y - mean) rstd m2), the BatchNorm backward when the rows
+ *   are all of its rows (conv5: count = rows).  For a level y = e, rows = N, count = 20 N and the two gathers below finish the step.
+ * pfpp_dgcnn_edge_bwd_dv / pfpp_dgcnn_edge_bwd_du (autograd of get_graph_feature_dynamic + conv_l + max, :41-56, :189-203): with n_i the
+ *   real slots of i and c_p the number of (i, j) with idx_ij = p,
+ *     dv[i] = a (h_i [the winning slot of i is real] - n_i m1 - m2 rstd (sum_{j real} u[idx_ij] + n_i (v[i] - mean)))
+ *     du[p] = a (sum_{(i,j): idx_ij = p} h_i [winner_i = j] - c_p m1 - m2 rstd (c_p (u[p] - mean) + sum_{(i,j): idx_ij = p} v[i]))
+ *   written to duv [N, 2 C_out] = du | dv.  du walks inverse lists: the flat positions e = 20 i + j whose index is p are
+ *   ent[off[p] .. off[p + 1]), of any length (n_ent = the number of real slots; the padded slots have no list).  The sums run in fp64
+ *   in list order and are rounded once.                                                                                           */
+#define PFPP_DGCNN_TRAIN_MAX_WG 1024
+#define PFPP_DGCNN_TRAIN_WS_DOUBLES (PFPP_DGCNN_TRAIN_MAX_WG * 512 + 1024)
+int pfpp_dgcnn_edge_stats(const float* uv, int64_t ld, const int32_t* idx, const float* gamma, const float* beta, double eps, double momentum,
+                          float* running_mean, float* running_var, int64_t N, int64_t C_out, int64_t K, float* e, unsigned char* winner,
+                          float* coef, double* workspace, pfpp_stream_t stream);
+int pfpp_dgcnn_bn_leaky_apply(const float* y, int64_t rows, int64_t C, int64_t ld, const float* coef, float slope, float* out, int64_t ldo,
+                              pfpp_stream_t stream);
+int pfpp_dgcnn_bn_leaky_bwd(const float* y, int64_t ld, const float* g1, int64_t ldg1, const float* g2, int64_t ldg2, int64_t rows, int64_t C,
+                            const float* coef, float slope, double count, float* h, float* dgamma, float* dbeta, float* means, float* dy,
+                            double* workspace, pfpp_stream_t stream);
+int pfpp_dgcnn_edge_bwd_dv(const float* uv, int64_t ld, const int32_t* idx, const unsigned char* winner, const float* h, const float* coef,
+                           const float* means, int64_t N, int64_t C_out, int64_t K, float* duv, pfpp_stream_t stream);
+int pfpp_dgcnn_edge_bwd_du(const float* uv, int64_t ld, const int64_t* off, const int32_t* ent, int64_t n_ent, const unsigned char* winner,
+                           const float* h, const float* coef, const float* means, int64_t N, int64_t C_out, int64_t K, float* duv,
+                           pfpp_stream_t stream);
+
 /* ---- matcher head, training behind part_feats (Jigsaw_matching/model/jigsaw/joint_seg_align_model.py in .train(); csrc/matching_train.hip)
  * Train-mode BatchNorm + ReLU, the linear layers, the affinity products and Adam go through pfpp_bn_stats / pfpp_bn_apply /
  * pfpp_bn_relu_bwd, pfpp_gemm / pfpp_gemm_grad and pfpp_adamw; these entries are the rest of the step.

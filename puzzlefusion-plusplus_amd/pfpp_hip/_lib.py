@@ -353,6 +353,12 @@ SIGNATURES = {
     "pfpp_dgcnn_knn": [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _p],
     "pfpp_dgcnn_edge_max": [_p, _i64, _p, _p, _p, _f32, _i64, _i64, _i64, _p, _i64, _p],
     "pfpp_leaky_relu": [_p, _i64, _i64, _i64, _f32, _p],
+    # ---- matcher front end, training: DGCNN encoder in .train() (dgcnn.py:41-56, 130-213; csrc/dgcnn_train.hip)
+    "pfpp_dgcnn_edge_stats": [_p, _i64, _p, _p, _p, C.c_double, C.c_double, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "pfpp_dgcnn_bn_leaky_apply": [_p, _i64, _i64, _i64, _p, _f32, _p, _i64, _p],
+    "pfpp_dgcnn_bn_leaky_bwd": [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _f32, C.c_double, _p, _p, _p, _p, _p, _p, _p],
+    "pfpp_dgcnn_edge_bwd_dv": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p],
+    "pfpp_dgcnn_edge_bwd_du": [_p, _i64, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p],
     # ---- matcher head, training (csrc/matching_train.hip)
     "pfpp_sinkhorn_train_fwd": [_p, _i64, _i64, _f32, _i64, _p, _p, _p, _p, _p, _p, _i64, _p],
     "pfpp_sinkhorn_train_bwd": [_p, _i64, _i64, _f32, _i64, _p, _p, _p, _f32, _p, _i64, _p, _i64, _p],

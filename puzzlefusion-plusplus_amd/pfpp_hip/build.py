@@ -59,6 +59,7 @@ SOURCES = {
     "matching_dataset.hip": ["-ffp-contract=off"],
     "matching_assign.hip": ["-ffp-contract=off"],
     "dgcnn.hip": ["-ffp-contract=off"],
+    "dgcnn_train.hip": ["-ffp-contract=off"],
 }
 # -fma-mix-insts (target feature off): without it the compiler may fold `(_Float16)(a * b + c)` into v_fma_mixlo_f16 — ONE rounding of
 # the exact value — while the `x - (float)hi` of the same hi / lo split goes through `v_cvt_f16_f32(RN32(x))`: in the rare
