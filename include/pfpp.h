@@ -1555,6 +1555,46 @@ int pfpp_match_assign(int64_t B, const float* const* c, const int64_t* n, const 
                       int32_t* status, int64_t* steps, int64_t* augmentations, void* workspace, int64_t workspace_bytes,
                       pfpp_stream_t stream);
 
+/* ---- matcher, edges and correspondences: the pair rule of compute_global_transformation on the device
+ * (Jigsaw_matching/model/modules/matching_base_model.py:298-359 up to the _save_data call, which turns the assignment into `edges` and
+ * per-edge correspondence lists one puzzle at a time on the host), together with the flattening of those lists that the assembly
+ * loop does before its edge features (puzzlefusion_plusplus/auto_aggl.py:92-126 here, get_distance_for_matching_pts,
+ * utils/node_merge_utils.py:62-89, in the reference); csrc/matching_edges.hip.  All B puzzles of a batch in one launch, a workgroup
+ * per puzzle; integer arithmetic only; bit for bit pfpp_hip.matching_edges.pack_matches_reference.
+ * Inputs (device, in the dtypes the head holds them): col int64 [total_rows] = the assignment as pfpp_match_assign writes it, one
+ * column per row, local to the puzzle, -1 = unmatched; row_off int64 [B + 1]: puzzle b owns the N'_b = row_off[b + 1] - row_off[b]
+ * rows from row_off[b] (zero rows: no edges); n_critical_pcs int64 [B, P]; n_valid int64 [B]; piece_off int64 [B P + 1] = point
+ * offsets of the pieces in slot order (pfpp_hip.matching.Layout.piece_off); critical_pcs_idx int64 [total_points], flat.
+ * max_rows >= every N'_b, total_rows and total_points are stated by the HOST; a puzzle whose device-side sizes contradict them
+ * or each other gets status 2 and is not read further.
+ * The rule, for every idx1 < idx2 < n_valid with critical points in both pieces: the block (rows of idx1, columns of idx2) of the
+ * assignment, or its transposed opposite (rows of idx2, columns of idx1) when that holds STRICTLY more matches; a pair with fewer
+ * than 3 matches is dropped; its rows (ordinal in idx1, ordinal in idx2) in lexicographic order.
+ * Outputs (device, int32, as pfpp_edge_histogram takes them), T = P (P - 1) / 2 triangle slots in row-major order:
+ *   counts [B, P, P]     matches per (piece of the row, piece of the column)
+ *   edge_off [B, T + 1]  offsets of the slots' correspondences, relative to the puzzle's slice; a dropped pair is an empty range
+ *   kept [B, T]          1 = the slot is an edge
+ *   corr [total_rows, 2] the piece-local critical ordinals (what the matching_data file holds), puzzle b from row row_off[b]
+ *   idx_a, idx_b [total_rows]  point indices within the puzzle: start(part) + critical_pcs_idx[start(part) + ordinal]
+ *   status [B]           0 fine; 1 col is not injective on its matched rows; 2 an entry of col outside [-1, N'_b), or sizes that
+ *                        contradict each other (N'_b > max_rows or > sum n_critical_pcs, n_valid outside [0, P], an n_critical_pcs
+ *                        outside [0, points of the piece], offsets that decrease or leave the stated totals)
+ * The kept blocks are disjoint sets of rows, so a puzzle has at most N'_b correspondences and its slice of corr / idx_a / idx_b is
+ * its slice of col; entries behind its last correspondence are not written.  A puzzle with non-zero status gets zero counts and no
+ * edges.  A puzzle's result does not depend on the rest of the batch; two runs agree bitwise; no loop is unbounded.
+ * PFPP_EUNSUPPORTED before any launch for P outside 1..PFPP_MATCH_EDGES_MAX_P, max_rows > PFPP_MATCH_EDGES_MAX_ROWS or
+ * B > PFPP_MATCH_EDGES_MAX_PUZZLES; B = 0 does nothing.  workspace (the inverse permutation, kept in global memory so that N' is
+ * not bounded by LDS): pfpp_match_edges_workspace(total_rows) bytes (-1 for a negative count), 4-byte aligned; corr 8-byte aligned.
+ * col, corr, idx_a, idx_b and workspace may be null when total_rows = 0, critical_pcs_idx when total_points = 0.                  */
+#define PFPP_MATCH_EDGES_MAX_P 32
+#define PFPP_MATCH_EDGES_MAX_ROWS 65535
+#define PFPP_MATCH_EDGES_MAX_PUZZLES 65535
+int64_t pfpp_match_edges_workspace(int64_t total_rows);
+int pfpp_match_edges(const int64_t* col, const int64_t* row_off, const int64_t* n_critical_pcs, const int64_t* n_valid,
+                     const int64_t* piece_off, const int64_t* critical_pcs_idx, int64_t B, int64_t P, int64_t max_rows,
+                     int64_t total_rows, int64_t total_points, int32_t* counts, int32_t* edge_off, int32_t* kept, int32_t* corr,
+                     int32_t* idx_a, int32_t* idx_b, int32_t* status, void* workspace, int64_t workspace_bytes, pfpp_stream_t stream);
+
 /* ---- matcher middle, training: the backward of the cross-attention layer tf_cross1 (Jigsaw_matching/model/jigsaw/attention_layer.py in
  * .train() under autograd; csrc/matching_tf_train.hip).  The layer has no dropout (:15, :44, :86, :92 are commented out) and its
  * norms are nn.LayerNorm: its training-time forward is the eval forward.  The linear layers' gradients go through pfpp_gemm in its

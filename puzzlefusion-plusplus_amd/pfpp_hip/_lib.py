@@ -379,6 +379,8 @@ SIGNATURES = {
     "pfpp_match_val_metrics": [_p, _i64, _p, _p, _p, _p, _p],
     # ---- matcher, assignment on the device (csrc/matching_assign.hip)
     "pfpp_match_assign": [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
+    # ---- matcher, edges and correspondences on the device (csrc/matching_edges.hip)
+    "pfpp_match_edges": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
     # ---- matcher middle, training (csrc/matching_tf_train.hip)
     "pfpp_attn_rows16_train": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
     "pfpp_attn_rows16_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p],
@@ -431,6 +433,7 @@ PLAIN = {
     "pfpp_match_colsum_ordered_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_ransac_pairs_workspace": ([_i64, _i64], C.c_int64),
     "pfpp_match_assign_workspace": ([_i64, _p], C.c_int64),
+    "pfpp_match_edges_workspace": ([_i64], C.c_int64),
 }
 
 # struct name in include/pfpp.h (without the pfpp_ prefix) -> its mirror here; load() compares the sizes

@@ -58,6 +58,7 @@ SOURCES = {
     "matching_pose.hip": ["-ffp-contract=off"],
     "matching_dataset.hip": ["-ffp-contract=off"],
     "matching_assign.hip": ["-ffp-contract=off"],
+    "matching_edges.hip": [],
     "dgcnn.hip": ["-ffp-contract=off"],
     "dgcnn_train.hip": ["-ffp-contract=off"],
 }

@@ -1,13 +1,15 @@
 """matching_data from point clouds or from per-point descriptors on one GPU — the reference's matcher (Jigsaw_matching/, test run)
 
     python -m pfpp_hip.generate_matching_data (--points DIR | --features DIR) --checkpoint CKPT --out DIR [--batch-size 16]
-                                              [--gemm f32|f16x3] [--seed S]
+                                              [--gemm f32|f16x3] [--seed S] [--assignment host|device] [--edges host|device]
 
 --points reads one DIR/<data_id>.npz per puzzle (part_pcs float32 [N_sum, 3]: the pieces' points as the matcher sees them, gt_pcs
 float32 [N_sum, 3], n_pcs int64 [P], part_valids [P]) and runs pfpp_hip.matching.DescriptorNetwork (encoder, tf_self1, tf_cross1) in
 front of the head; --features reads the descriptors themselves (part_feats float32 [N_sum, 128] in place of part_pcs: the seam
 between the two).  Either way pfpp_hip.matching.MatchingHead runs in batches and OUT/<data_id>.npz is written
-through pfpp_hip.io.save_matching_data.  A file that exists is left alone and its puzzle is not computed."""
+through pfpp_hip.io.save_matching_data.  A file that exists is left alone and its puzzle is not computed.  --edges device builds
+the files' edges and correspondences of a whole batch in one launch (pfpp_hip.matching_edges) instead of per puzzle on the host; the
+files hold the same arrays."""
 from __future__ import annotations
 
 import argparse
@@ -91,6 +93,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--seed", type=int, default=0, help="--points: seed of the encoder's sampling starts (the reference draws them at random)")
     ap.add_argument("--assignment", choices=("host", "device"), default="host",
                     help="the optimal assignment: scipy on the host, or the batched exact solver on the GPU (pfpp_hip.matching_assign)")
+    ap.add_argument("--edges", choices=("host", "device"), default="host",
+                    help="the pair rule that turns the assignment into edges and correspondences: numpy per puzzle on the host, or one "
+                         "launch per batch on the GPU (pfpp_hip.matching_edges)")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be at least 1")
@@ -113,6 +118,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         print("generate_matching_data: no GPU: the matching kernels run on the GPU only", file=sys.stderr)
         return 2
     from pfpp_hip.matching import match_edges, write_matching_data
+    from pfpp_hip.matching_edges import match_edges_batch
 
     t0, n, host, device = time.perf_counter(), 0, 0.0, 0.0
     for ids, items, n_pcs, valids, out in head_batches(source, args.points is not None, args.checkpoint, args.gemm, args.seed, todo, args.batch_size,
@@ -120,9 +126,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         host += out.timings["host_assignment_s"]
         device += out.timings["device_assignment_s"]
         nc = out.n_critical_pcs.cpu().numpy()
+        n_valid = [int(np.asarray(x["part_valids"]).sum()) for x in items]
+        dm = match_edges_batch(out.perm_mat, out.n_critical_pcs, n_valid, n_pcs, out.critical_pcs_idx) if args.edges == "device" else None
         for b, (d, x) in enumerate(zip(ids, items)):
             p = x["n_pcs"].shape[0]
-            edges, corr = match_edges(out.perm_mat[b], nc[b], int(np.asarray(x["part_valids"]).sum()))
+            edges, corr = dm.files(b) if dm is not None else match_edges(out.perm_mat[b], nc[b], n_valid[b])
             write_matching_data(args.out, d, edges=edges, correspondence=corr, gt_pcs=x["gt_pcs"], critical_pcs_idx=out.critical_pcs_idx[b],
                                 n_pcs=x["n_pcs"], n_critical_pcs=nc[b, :p])
             n += 1

@@ -8,7 +8,8 @@ and model/modules/matching_base_model.py:298-361, 614-640 up to the file:
   with solver="device" the exact batched solver of pfpp_hip/matching_assign.py instead).
 * sinkhorn / fracture_labels: the two kernels on their own.
 * match_edges: the piece-pair rule that turns the assignment into `edges` and `correspondence` (host: O(N') integer work on an
-  array the host already holds for the assignment).
+  array the host already holds for the assignment; pfpp_hip.matching_edges runs the same rule on the device for an assignment
+  that was solved there).
 * write_matching_data: the file, through io.save_matching_data; an existing file is left alone, as in the reference.
 """
 from __future__ import annotations

@@ -409,8 +409,11 @@ class _PuzzleState:
         self.nodes = [{"pivot": i, "valids": True, "ref_part": False, "init_pose": None} for i in range(self.n_nodes)]
         self.nodes[int(torch.where(self.ref_part)[1][0])]["ref_part"] = True
         self.classified = torch.zeros_like(self.part_valids, dtype=torch.bool)
-        self.have_matching = "edges" in data_dict
-        self.match = model.prepare_matching(data_dict, dev) if self.have_matching else None
+        # "matching_prepared": prepare_matching's dict built on the device (pfpp_hip.matching_edges.DeviceMatches.prepared): the
+        # correspondence lists of the file are then neither needed nor read
+        prepared = data_dict.get("matching_prepared")
+        self.have_matching = prepared is not None or "edges" in data_dict
+        self.match = prepared if prepared is not None else model.prepare_matching(data_dict, dev) if self.have_matching else None
         self.pivot = torch.arange(self.n_nodes, dtype=torch.int32, device=dev)
         self.edge_indices = model._edge_pairs(P, dev)[None]          # == triu(ones, 1).nonzero(): row-major upper triangle
         self.edge_valids = model._edge_mask(self.num_parts, P)

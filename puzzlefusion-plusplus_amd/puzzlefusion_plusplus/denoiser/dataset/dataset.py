@@ -23,7 +23,10 @@ from pfpp_hip.scheduler import PiecewiseScheduler
 
 
 class GeometryLatentDataset(Dataset):
-    def __init__(self, cfg, data_dir, overfit, data_fn, device_augment: bool = False):
+    def __init__(self, cfg, data_dir, overfit, data_fn, device_augment: bool = False, matching=None):
+        """matching: in test mode, a mapping data_id -> a dict shaped like pfpp_hip.io.load_matching_data's, used in place of the
+        files under cfg.data.matching_data_path (a caller that ran the matcher itself joins its output to pc_data without writing
+        files; entries it adds beyond the file's keys travel with the sample).  None: the directory, as in the reference."""
         self.cfg = cfg
         self.mode = data_fn
         self.data_dir = data_dir
@@ -34,11 +37,17 @@ class GeometryLatentDataset(Dataset):
         if overfit != -1:
             files = files[:overfit]
         self.data_files = files
-        matching_dir = cfg.data.matching_data_path if self.mode == "test" else None
+        if matching is not None and self.mode != "test":
+            raise ValueError("matching: only the test split carries matching data")
+        matching_dir = cfg.data.matching_data_path if self.mode == "test" and matching is None else None
         self.data_list = []
         for name in files:
             sample = pfio.load_pc_data(os.path.join(data_dir, name))
             sample.pop("category", None)
+            if matching is not None:
+                if sample["data_id"] not in matching:
+                    continue                                     # as for a missing file
+                sample.update(matching[sample["data_id"]])
             if matching_dir is not None:
                 mpath = os.path.join(matching_dir, f"{sample['data_id']}.npz")
                 if not os.path.exists(mpath):
