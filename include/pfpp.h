@@ -336,7 +336,8 @@ int pfpp_gemm_dw_group(const pfpp_dw_job* jobs, int32_t n_jobs, int64_t K, int32
  * reduction followed): lets a profiler-side tool attribute event timings to kernel names.  gemm_pl_kernel's eighth field is a
  * constant 0 (a template parameter that no longer exists; the positions of the others are kept).  pfpp_sa_train_stage and the
  * attention entry points (pfpp_attn_dense*, pfpp_attn_blockdiag*) report here too: several launches of one call joined with '+' in
- * launch order, "" after a refused call */
+ * launch order, "" after a refused call.  So do pfpp_gemm_wd / _f16 and pfpp_gemm_small / _v (the calls a sequencer such as
+ * pfpp_tlayers_eval makes included: after it, the name is that of its last such GEMM) */
 const char* pfpp_last_gemm_kernel(void);
 
 /* ---- a4 + a5 + a6 fused, for a set-abstraction level without input features ---------------------------
@@ -1047,9 +1048,14 @@ int pfpp_embed_tokens_small(const float* latent, const float* xyz, const float* 
  * with its fragment-blocked planes (fhi / flo).  The out-projections of both attentions and the second feed-forward linear with their
  * residual adds (attention.py:77-90), eval mode; out may be the residual (in place).  K % 512 == 0, N % 32 == 0.  Same products as
  * pfpp_gemm's split-f16 path, one k-ordered chain per output (equal to it to fp32 rounding); pfpp_tlayers_eval uses it for
- * M <= lnlin_max_rows.                                                                                                              */
+ * M <= lnlin_max_rows.  Kernel choice (csrc/gemm_small.hip choose_gemm_small, reported by pfpp_last_gemm_kernel): the contraction
+ * split over eight waves (gemm_small_ks_kernel<8, 2>) for K = 2048 at M <= 512, one chain per output (gemm_small_kernel) otherwise.
+ * pfpp_gemm_small_v: variant 0 = that choice (what pfpp_gemm_small passes), 1 = the one-chain kernel at every shape (the cross-check
+ * of the split kernel), anything else PFPP_EINVAL.  No environment variable selects a kernel here or in pfpp_gemm_wd.              */
 int pfpp_gemm_small(const pfpp_planes* A, int64_t lda, const pfpp_pw* w, const float* bias, const float* residual, int64_t ldr, float* out,
                     int64_t ldc, int64_t M, int64_t N, int64_t K, pfpp_stream_t stream);
+int pfpp_gemm_small_v(const pfpp_planes* A, int64_t lda, const pfpp_pw* w, const float* bias, const float* residual, int64_t ldr, float* out,
+                      int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t variant, pfpp_stream_t stream);
 /* The same operation above the few-token range, weights never staged through LDS (csrc/gemm_wd.hip): out [M, ldc] = (A . W^T) / (A.scale *
  * w.scale) + bias + residual with A = row-major planes [M, lda] and w's fragment-blocked planes read straight into the matrix operands
  * (attn.to_q|k|v / attn.to_out[0] / ff.net[2] of attention.py:77-90, eval mode: static weights).  N % 128 == 0, K % 32 == 0, 16-byte

@@ -15,8 +15,6 @@
 //   * bias and residual are fetched before the contraction starts and added from registers (out may alias the residual).
 // Arithmetic: the split-f16 products of pfpp_gemm (small terms first) in k order, one chain per output: equal to the tiled GEMM to fp32
 // rounding (another association of the same products), deterministic.
-#include <stdlib.h>
-
 #include "pfpp_common.h"
 
 namespace {
@@ -206,11 +204,27 @@ __global__ __launch_bounds__(64 * NW) void gemm_small_ks_kernel(GsP p) {
   }
 }
 
+// ---- which kernel: a pure function of the shape and the caller's variant (0 = this rule, 1 = the one-chain kernel: the cross-check
+// of gemm_small_ks_kernel).  The contraction split over the waves for the depth of the path, while the row tiles leave most of the chip
+// idle.  Measured (tools/diag/small_time.py, dependent launches, N = 512): K = 2048 at 200 / 500 rows 20.7 -> 14.5 us, at 1,000 rows
+// 21 -> 26 (every unit's workgroup re-reads the row tile's A planes); K = 512 is at the launch floor either way (7.5 - 8.2 us) and keeps
+// the chain
+enum class SmallKern { Chain, KSplit };
+constexpr int64_t SMALL_KS_K = 2048;            // the one depth the split kernel is instantiated for (8 waves x 2 rounds of 128)
+constexpr int64_t SMALL_KS_MAX_ROWS = 512;
+
+SmallKern choose_gemm_small(int64_t M, int64_t /* N: no rule reads the width */, int64_t K, int variant) {
+  return variant == 0 && K == SMALL_KS_K && M <= SMALL_KS_MAX_ROWS ? SmallKern::KSplit : SmallKern::Chain;
+}
+
 }  // namespace
 
-extern "C" int pfpp_gemm_small(const pfpp_planes* A, int64_t lda, const pfpp_pw* w, const float* bias, const float* residual, int64_t ldr,
-                               float* out, int64_t ldc, int64_t M, int64_t N, int64_t K, pfpp_stream_t stream) {
+extern "C" int pfpp_gemm_small_v(const pfpp_planes* A, int64_t lda, const pfpp_pw* w, const float* bias, const float* residual, int64_t ldr,
+                                 float* out, int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t variant, pfpp_stream_t stream) {
+  using pfpp_gemm_detail::KernelName;
+  pfpp_gemm_detail::report_no_kernel();
   PFPP_REQUIRE(A && A->hi && A->lo && w && out, "null pointer");
+  PFPP_REQUIRE(variant == 0 || variant == 1, "variant: 0 (the library's choice) or 1 (the one-chain kernel)");
   PFPP_REQUIRE(w->fhi && w->flo && pfpp::aligned16(w->fhi) && pfpp::aligned16(w->flo), "the weight's fragment-blocked planes (pfpp_pw.fhi / flo) are required");
   PFPP_SUPPORTED(K % KA == 0 && K >= KA && N % 32 == 0 && N >= 32, "K % 512 != 0 or N % 32 != 0");
   PFPP_REQUIRE(M >= 1 && M <= 0x7fffffff && lda >= K && lda % 8 == 0 && ldc >= N && (!residual || ldr >= N), "sizes / leading dimensions");
@@ -221,20 +235,29 @@ extern "C" int pfpp_gemm_small(const pfpp_planes* A, int64_t lda, const pfpp_pw*
   p.inv_scale = 1.0f / (A->scale * w->scale);
   p.bias = bias; p.res = residual; p.ldr = ldr; p.out = out; p.ldc = ldc;
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  // contraction split over the waves (gemm_small_ks_kernel) for the depths of the path, while the row tiles leave most of the chip idle;
-  // PFPP_GEMM_SMALL_KS=0: the one-chain kernel everywhere (cross-check)
-  const char* ks_env = getenv("PFPP_GEMM_SMALL_KS");
-  // measured (tools/diag/small_time.py, dependent launches, N = 512): K = 2048 at 200 / 500 rows 20.7 -> 14.5 us, at 1,000 rows 21 -> 26
-  // (every unit's workgroup re-reads the row tile's A planes); K = 512 is at the launch floor either way (7.5 - 8.2 us) and keeps the chain
-  const bool ks = !(ks_env && atoi(ks_env) == 0) && K == 2048 && M <= 512;
-  if (ks) {
-    const dim3 gk((unsigned)((M + 31) / 32), (unsigned)(N / 32));
-    hipLaunchKernelGGL((gemm_small_ks_kernel<8, 2>), gk, dim3(512), (size_t)8 * 16 * 64 * sizeof(float), pfpp::as_stream(stream), p);
-    return pfpp::check_launch(__func__);
+  hipStream_t st = pfpp::as_stream(stream);
+  switch (choose_gemm_small(M, N, K, variant)) {
+    case SmallKern::KSplit: {
+      static const KernelName name("gemm_small_ks_kernel<8, 2>");
+      pfpp_gemm_detail::report_kernel(name);
+      const dim3 grid((unsigned)((M + 31) / 32), (unsigned)(N / 32));
+      hipLaunchKernelGGL((gemm_small_ks_kernel<8, 2>), grid, dim3(512), (size_t)8 * 16 * 64 * sizeof(float), st, p);
+      break;
+    }
+    case SmallKern::Chain: {
+      const size_t smem = (size_t)2 * 2 * 32 * LKP * sizeof(_Float16);
+      if (pfpp_allow_dyn_lds<gemm_small_kernel>((int)smem) != hipSuccess) break;
+      static const KernelName name("gemm_small_kernel");
+      pfpp_gemm_detail::report_kernel(name);
+      const dim3 grid((unsigned)((M + 31) / 32), (unsigned)((N / 32 + 3) / 4));
+      hipLaunchKernelGGL(gemm_small_kernel, grid, dim3(256), smem, st, p);
+      break;
+    }
   }
-  const size_t smem = (size_t)2 * 2 * 32 * LKP * sizeof(_Float16);
-  if (pfpp_allow_dyn_lds<gemm_small_kernel>((int)smem) != hipSuccess) return pfpp::check_launch(__func__);
-  const dim3 grid((unsigned)((M + 31) / 32), (unsigned)((N / 32 + 3) / 4));
-  hipLaunchKernelGGL(gemm_small_kernel, grid, dim3(256), smem, pfpp::as_stream(stream), p);
-  return pfpp::check_launch(__func__);
+  return pfpp::check_launch("pfpp_gemm_small");
+}
+
+extern "C" int pfpp_gemm_small(const pfpp_planes* A, int64_t lda, const pfpp_pw* w, const float* bias, const float* residual, int64_t ldr,
+                               float* out, int64_t ldc, int64_t M, int64_t N, int64_t K, pfpp_stream_t stream) {
+  return pfpp_gemm_small_v(A, lda, w, bias, residual, ldr, out, ldc, M, N, K, 0, stream);
 }

@@ -204,6 +204,7 @@ SIGNATURES = {
     "pfpp_tlayers_eval": [C.POINTER(TlayersEvalArgs), _p],
     "pfpp_embed_tokens_small": [_p, _p, _p, _p, _p, C.POINTER(PwC), _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "pfpp_gemm_small": [_pl, _i64, C.POINTER(PwC), _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p],
+    "pfpp_gemm_small_v": [_pl, _i64, C.POINTER(PwC), _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i32, _p],
     "pfpp_gemm_wd": [_pl, _i64, C.POINTER(PwC), _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p],
     "pfpp_gemm_wd_supported": [_i64, _i64, _i64],
     "pfpp_gemm_wd_f16": [_pl, _i64, C.POINTER(PwC), _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p],

@@ -9,8 +9,9 @@ down-projection (+bias, +residual).
 """
 from __future__ import annotations
 
+import dataclasses
+import enum
 import math
-import os
 from typing import Dict, Optional
 
 import torch
@@ -65,38 +66,111 @@ def pack_denoiser(sd: Dict[str, torch.Tensor], num_layers: int) -> Dict[str, tor
     return pk
 
 
-def _fused_heads(pk, pooled, out, slot32=None) -> bool:
-    """pool -> both output heads in one launch (csrc/heads.hip); False when the mode / shape is not the fused kernel's (exact-fp32
-    mode, PFPP_HEADS_FUSED=0, width != 512): the caller then runs the layer-wise GEMMs"""
-    import os
+# ---- which path an eval / sampler step takes: one plan, chosen by a pure function of the call's facts (no process-wide switch
+# selects anything here; the arithmetic modes PFPP_GEMM, PFPP_SPLIT_ACT and ops.SINGLE_PASS are inputs of the choice)
+# <= this many tokens: the few-token kernels (LayerNorm inside the next GEMM, pfpp_gemm_small, the one-launch embedding); above it the
+# C sequencer takes the weight-direct GEMMs (pfpp_gemm_wd)
+EVAL_FEW_TOKEN_MAX_ROWS = 2048
 
+
+class EvalBlocks(enum.Enum):
+    C_SEQUENCED = "c"        # the transformer blocks enqueued by one foreign call (pfpp_tlayers_eval; compact forward only)
+    PY_TILED = "py_tiled"    # issued from Python, every linear through the tiled GEMM (any mode, any width; the cross-check)
+    PY_WD = "py_wd"          # issued from Python, qkv / out-projection / second feed-forward linear through pfpp_gemm_wd
+
+
+@dataclasses.dataclass(frozen=True)
+class EvalPlan:
+    embed_fused: bool        # features, both embedding layers and the combine in one launch (csrc/embed_small.hip)
+    blocks: EvalBlocks
+    lnlin_max_rows: int      # C_SEQUENCED: up to this many tokens the few-token kernels (0 = never: the launches of the Python sequence)
+    wd_gemm: bool            # C_SEQUENCED: above lnlin_max_rows the weight-direct GEMMs (the Python sequences say it in `blocks`)
+    heads_fused: bool        # pool -> both output heads in one launch (csrc/heads.hip) instead of the layer-wise GEMMs
+
+
+def frag_covers_blocks(C: int, inner: int) -> bool:
+    """does the fragment-blocked layout (packing.PW.frag: N % 32 == 0 and K % 16 == 0) cover every block weight?  wqkv [3C, C],
+    wo [C, C], ff.w1 [2 inner, C], ff.w2 [C, inner]"""
+    return C % 32 == 0 and (2 * inner) % 32 == 0 and inner % 16 == 0
+
+
+def _wd_covers_blocks(C: int, inner: int) -> bool:
+    """pfpp_gemm_wd_supported for wqkv, wo and ff.w2: N % 128 == 0, K % 32 == 0"""
+    return C % 128 == 0 and inner % 32 == 0
+
+
+def choose_eval(*, compact: bool, gemm_mode: str, split_act: bool, single_pass: bool, traced: bool, tokens: int, C: int, inner: int,
+                L: int, latent_dim: int, embed_packed: bool) -> EvalPlan:
+    """the plan of denoiser_forward_compact (compact) / denoiser_forward (all slots) when the caller names none.  traced = bench.py's
+    per-launch timing pass (ops.GEMM_TRACE set): it issues the blocks from Python and then takes the weight-direct GEMMs
+    pfpp_tlayers_eval takes, so that the roofline object describes the kernels of the timed region.  The all-slots forward never takes
+    them by itself: with all 640 slots evaluated (16,000 tokens) the 256 x 128 tiled kernel has enough tiles per CU that its LDS traffic
+    is not the bound, 6.756 vs 6.751 ms per sampler step (profiles/r04zw_ab_wd_full.txt) — blocks = PY_WD by argument only."""
+    split = gemm_mode == "f16x3" and split_act
+    heads_fused = gemm_mode == "f16x3" and C == 512
+    if not compact:
+        return EvalPlan(embed_fused=False, blocks=EvalBlocks.PY_TILED, lnlin_max_rows=0, wd_gemm=False, heads_fused=heads_fused)
+    few = tokens <= EVAL_FEW_TOKEN_MAX_ROWS
+    embed_fused = few and embed_packed and split and not single_pass and not traced and L >= 11 and latent_dim == 64 and C % 32 == 0
+    if split and not traced and frag_covers_blocks(C, inner):
+        return EvalPlan(embed_fused=embed_fused, blocks=EvalBlocks.C_SEQUENCED, lnlin_max_rows=EVAL_FEW_TOKEN_MAX_ROWS, wd_gemm=True,
+                        heads_fused=heads_fused)
+    wd = traced and split and not single_pass and not few and _wd_covers_blocks(C, inner)
+    return EvalPlan(embed_fused=embed_fused, blocks=EvalBlocks.PY_WD if wd else EvalBlocks.PY_TILED, lnlin_max_rows=0, wd_gemm=wd,
+                    heads_fused=heads_fused)
+
+
+def check_plan(plan: EvalPlan, *, compact: bool, gemm_mode: str, split_act: bool, single_pass: bool, traced: bool, tokens: int, C: int,
+               inner: int, L: int, latent_dim: int, embed_packed: bool) -> None:
+    """ValueError for a plan this call cannot honour (before anything is launched): every kernel a plan names has its own modes and
+    widths, and nothing falls back quietly"""
+    split = gemm_mode == "f16x3" and split_act
+    no = []
+    if plan.embed_fused and not (compact and embed_packed and split and not single_pass and L >= 11 and latent_dim == 64 and C % 32 == 0):
+        no.append("embed_fused: compact forward, 148 + 147 input features, split-f16 planes without single pass, L >= 11, latent 64, C % 32 == 0")
+    if plan.blocks is EvalBlocks.C_SEQUENCED and not (compact and split and not traced and frag_covers_blocks(C, inner)):
+        no.append("C_SEQUENCED: compact forward in the split-f16 plane mode, untraced, widths the fragment-blocked layout covers")
+    if plan.blocks is EvalBlocks.PY_WD and not (split and not single_pass and _wd_covers_blocks(C, inner)):
+        no.append("PY_WD: split-f16 plane mode without single pass, C % 128 == 0, inner % 32 == 0")
+    if plan.heads_fused and not (gemm_mode == "f16x3" and C == 512):
+        no.append("heads_fused: f16x3 mode at width 512")
+    if plan.lnlin_max_rows < 0:
+        no.append("lnlin_max_rows >= 0")
+    if no:
+        raise ValueError(f"EvalPlan not possible here ({gemm_mode}, C = {C}, inner = {inner}, {tokens} tokens) - " + "; ".join(no))
+
+
+def _plan_for(plan: Optional[EvalPlan], pk, *, compact: bool, tokens: int, C: int, inner: int, L: int, latent_dim: int) -> EvalPlan:
+    """the call's facts, gathered once: the default plan, or the caller's after check_plan"""
+    facts = dict(compact=compact, gemm_mode=ops.GEMM_MODE, split_act=ops.split_act(), single_pass=ops.SINGLE_PASS,
+                 traced=ops.GEMM_TRACE is not None, tokens=tokens, C=C, inner=inner, L=L, latent_dim=latent_dim,
+                 embed_packed="embed.w" in pk)
+    if plan is None:
+        return choose_eval(**facts)
+    check_plan(plan, **facts)
+    return plan
+
+
+def _fused_heads(pk, pooled, out, slot32=None) -> None:
+    """pool -> both output heads in one launch (csrc/heads.hip): f16x3 mode, width 512 (plan.heads_fused)"""
     from . import train_ops as T
 
-    if ops.GEMM_MODE != "f16x3" or os.environ.get("PFPP_HEADS_FUSED", "1") != "1" or pooled.shape[1] != 512:
-        return False
     hp = pk.get("_heads")
     if hp is None:
         hp = pk["_heads"] = tuple(T.head_params(pk[f"{n}.0.w"], pk[f"{n}.2.w"], pk[f"{n}.4.w"].f32, pk[f"{n}.0.b"], pk[f"{n}.2.b"],
                                                 pk[f"{n}.4.b"], static=True) for n in ("mlp_out_trans", "mlp_out_rot"))
     T.heads_fwd(pooled, hp[0], hp[1], out, slot=slot32)
-    return True
 
 
-def _eval_layers_c(pk, h, mods, lay, L: int, num_layers: int, num_heads: int, att_scale: float, inner: int) -> bool:
-    """the transformer blocks of the compact eval forward enqueued from C (pfpp_tlayers_eval, csrc/tlayer.hip): h is updated in place.
-    False when the mode is not the plane path's (exact fp32, fp32 hand-over, GEMM tracing, PFPP_EVAL_CSEQ=0): the caller then issues
-    the launches itself."""
+def _eval_layers_c(pk, h, mods, lay, L: int, num_layers: int, num_heads: int, att_scale: float, inner: int, plan: EvalPlan) -> None:
+    """the transformer blocks of the compact eval forward enqueued from C (pfpp_tlayers_eval, csrc/tlayer.hip): h is updated in place
+    (plan.blocks = C_SEQUENCED: the plane mode, widths the fragment-blocked layout covers)"""
     import ctypes as C_
-    import os
 
     from . import _lib
     from ._lib import ElayerParams, PlanesC, PwC, TlayersEvalArgs
 
-    if not ops.split_mode() or ops.GEMM_TRACE is not None or os.environ.get("PFPP_EVAL_CSEQ", "1") != "1":
-        return False
     st = pk.get("_cseq_eval")
-    if st is False:
-        return False
     if st is None:
         layers = (ElayerParams * num_layers)()
 
@@ -104,15 +178,10 @@ def _eval_layers_c(pk, h, mods, lay, L: int, num_layers: int, num_heads: int, at
             fh, fl = w.frag()          # (kept alive by the PW in pk)
             return PwC(w.f32.data_ptr(), w.hi.data_ptr(), w.lo.data_ptr(), w.scale, w.hi.shape[-1], fh.data_ptr(), fl.data_ptr())
 
-        try:
-            for i in range(num_layers):
-                for name, key in (("qkv1", f"{i}.self_attn.wqkv"), ("o1", f"{i}.self_attn.wo"), ("qkv2", f"{i}.global_attn.wqkv"),
-                                  ("o2", f"{i}.global_attn.wo"), ("ff1", f"{i}.ff.w1"), ("ff2", f"{i}.ff.w2")):
-                    setattr(layers[i], name, pw(pk[key]))
-        except ValueError:                 # a width the fragment-blocked layout does not cover (N % 32, K % 16): the Python sequence of
-            pk["_cseq_eval"] = False       # tiled launches serves any shape
-            return False
         for i in range(num_layers):
+            for name, key in (("qkv1", f"{i}.self_attn.wqkv"), ("o1", f"{i}.self_attn.wo"), ("qkv2", f"{i}.global_attn.wqkv"),
+                              ("o2", f"{i}.global_attn.wo"), ("ff1", f"{i}.ff.w1"), ("ff2", f"{i}.ff.w2")):
+                setattr(layers[i], name, pw(pk[key]))
             for name, key in (("bo1", f"{i}.self_attn.bo"), ("bo2", f"{i}.global_attn.bo"), ("g3", f"{i}.norm3.g"), ("b3", f"{i}.norm3.b"),
                               ("bff1", f"{i}.ff.b1"), ("bff2", f"{i}.ff.b2")):
                 setattr(layers[i], name, pk[key].data_ptr())
@@ -135,10 +204,8 @@ def _eval_layers_c(pk, h, mods, lay, L: int, num_layers: int, num_heads: int, at
     ws = ops._split_workspace(dev)
     args.split_ws, args.split_ws_bytes = ws[0].data_ptr(), ws[0].numel() * 4
     args.split_cnt, args.split_cnt_len = ws[1].data_ptr(), ws[1].numel()
-    args.lnlin_max_rows = int(os.environ.get("PFPP_EVAL_LNLIN_ROWS", "2048"))     # <= this many tokens: the few-token kernels (LayerNorm inside the next GEMM, pfpp_gemm_small)
-    args.wd_gemm = int(os.environ.get("PFPP_EVAL_WD", "1") == "1")               # above that: weights straight into the matrix operands (pfpp_gemm_wd)
+    args.lnlin_max_rows, args.wd_gemm = plan.lnlin_max_rows, int(plan.wd_gemm)
     _lib.check(_lib.load().pfpp_tlayers_eval(C_.byref(args), ops._stream()), "pfpp_tlayers_eval")
-    return True
 
 
 def dense_attention(qkv: torch.Tensor, B: int, T: int, H: int, dh: int, key_valid_u8: torch.Tensor,
@@ -261,7 +328,7 @@ def attach_layout(part_valids: torch.Tensor, L: int, layout: CompactLayout) -> N
 
 
 def denoiser_forward_compact(pk, x, timesteps, latent, xyz, part_valids, scale, ref_part, *, num_layers: int,
-                             num_heads: int, layout: Optional[CompactLayout] = None) -> torch.Tensor:
+                             num_heads: int, layout: Optional[CompactLayout] = None, plan: Optional[EvalPlan] = None) -> torch.Tensor:
     """DenoiserTransformer.forward restricted to the VALID fragments.
 
     In the reference every one of the P = 20 slots is a query (denoiser_transformer.py:173-185) but keys are
@@ -269,7 +336,8 @@ def denoiser_forward_compact(pk, x, timesteps, latent, xyz, part_valids, scale, 
     valid token ever depends on a padded one.  Dropping the padded slots therefore leaves the predicted noise of
     every valid fragment unchanged (same GEMM rows, same attention keys) and only replaces the reference's
     don't-care values at padded slots by 0 — at the benchmark's fragment distribution that is 4x fewer tokens.
-    Ragged per-puzzle sequences go through pfpp_attn_dense's (seq_off, seq_len)."""
+    Ragged per-puzzle sequences go through pfpp_attn_dense's (seq_off, seq_len).
+    plan: which kernels the step takes (None = choose_eval's; one this call cannot honour raises ValueError before any launch)."""
     B, P, L, _ = latent.shape
     C = pk["shape.b"].numel()
     n_slots = B * P
@@ -282,13 +350,13 @@ def denoiser_forward_compact(pk, x, timesteps, latent, xyz, part_valids, scale, 
     if Fv == 0:
         return out.view(B, P, 7)
     M = Fv * L
+    inner = pk["0.ff.w2"].K
+    plan = _plan_for(plan, pk, compact=True, tokens=M, C=C, inner=inner, L=L, latent_dim=latent.shape[-1])
     # the valid-fragment gather of the inputs happens inside the kernels (slot32): no gathered copies
     f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
     rp = ref_part.reshape(n_slots)
     ref_u8 = rp.contiguous().view(torch.uint8) if rp.dtype == torch.bool else (rp if rp.dtype == torch.uint8 else (rp != 0).to(torch.uint8)).contiguous()
-    few = int(os.environ.get("PFPP_EVAL_LNLIN_ROWS", "2048"))
-    if (M <= few and "embed.w" in pk and ops.split_mode() and not ops.SINGLE_PASS and ops.GEMM_TRACE is None and L >= 11 and latent.shape[-1] == 64
-            and os.environ.get("PFPP_EMBED_FUSED", "1") == "1"):
+    if plan.embed_fused:
         # few tokens: features, both embedding layers and the combine in one launch (csrc/embed_small.hip)
         h = ops.embed_tokens_small(f32(latent).reshape(n_slots, L, -1), f32(xyz).reshape(n_slots, L, 3), f32(scale).reshape(n_slots),
                                    f32(x).reshape(n_slots, 7), lay.slot32, pk["embed.w"], pk["embed.b"], pk["ref_emb"], ref_u8, pk["pe"],
@@ -302,18 +370,15 @@ def denoiser_forward_compact(pk, x, timesteps, latent, xyz, part_valids, scale, 
     n_ada = 2 * num_layers
     mods = ada_mods(pk, timesteps, n_ada, C)
     att_scale = 1.0 / math.sqrt(dh)
-    inner = pk["0.ff.w2"].K
-    in_c = _eval_layers_c(pk, h, mods, lay, L, num_layers, num_heads, att_scale, inner)
+    in_c = plan.blocks is EvalBlocks.C_SEQUENCED
+    wd = plan.blocks is EvalBlocks.PY_WD
     if in_c:
+        _eval_layers_c(pk, h, mods, lay, L, num_layers, num_heads, att_scale, inner, plan)
         norm = att = u_buf = None
     elif ops.split_mode():      # GEMM inputs produced by our own kernels travel as pre-split fp16 planes (see ops.split_mode)
         norm, att, u_buf = (ops.SplitAct.empty(M, C, dev), ops.SplitAct.empty(M, C, dev), ops.SplitAct.empty(M, inner, dev))
     else:
         norm, att, u_buf = torch.empty_like(h), torch.empty_like(h), None
-    # bench.py's per-launch timing pass issues the blocks from Python: it then takes the weight-direct GEMMs pfpp_tlayers_eval takes, so
-    # that the roofline object describes the kernels of the timed region (untraced, this sequence stays the tiled cross-check)
-    wd = (not in_c and ops.GEMM_TRACE is not None and ops.split_mode() and not ops.SINGLE_PASS and os.environ.get("PFPP_EVAL_WD", "1") == "1"
-          and os.environ.get("PFPP_EVAL_CSEQ", "1") == "1" and M > int(os.environ.get("PFPP_EVAL_LNLIN_ROWS", "2048")) and C % 128 == 0)
 
     def lin_res(a_, wkey, bkey, K_):
         if wd:
@@ -333,7 +398,8 @@ def denoiser_forward_compact(pk, x, timesteps, latent, xyz, part_valids, scale, 
         u = ops.linear(norm, pk[f"{i}.ff.w1"], pk[f"{i}.ff.b1"], act="geglu", out=u_buf)
         lin_res(u, f"{i}.ff.w2", f"{i}.ff.b2", inner)
     pooled = ops.mean_pool(h, Fv, L)
-    if _fused_heads(pk, pooled, out, lay.slot32):
+    if plan.heads_fused:
+        _fused_heads(pk, pooled, out, lay.slot32)
         return out.view(B, P, 7)
     out_c = torch.empty((Fv, 7), dtype=torch.float32, device=dev)
     for name, c0, width in (("mlp_out_trans", 0, 3), ("mlp_out_rot", 3, 4)):
@@ -346,8 +412,9 @@ def denoiser_forward_compact(pk, x, timesteps, latent, xyz, part_valids, scale, 
 
 
 def denoiser_forward(pk, x, timesteps, latent, xyz, part_valids, scale, ref_part, *, num_layers: int,
-                     num_heads: int, capture: Optional[dict] = None) -> torch.Tensor:
-    """DenoiserTransformer.forward (denoiser_transformer.py:169-203), eval mode."""
+                     num_heads: int, capture: Optional[dict] = None, plan: Optional[EvalPlan] = None) -> torch.Tensor:
+    """DenoiserTransformer.forward (denoiser_transformer.py:169-203), eval mode.  plan: as in denoiser_forward_compact; the blocks are
+    always issued from Python here (PY_TILED by default, PY_WD by argument: bit-identical)."""
     B, P, L, _ = latent.shape
     C = pk["shape.b"].numel()
     n = B * P
@@ -356,6 +423,8 @@ def denoiser_forward(pk, x, timesteps, latent, xyz, part_valids, scale, ref_part
     dh = C // num_heads
     if P > pk["pe"].shape[0]:
         raise ValueError(f"P={P} fragments exceed PositionalEncoding max_len={pk['pe'].shape[0]}")
+    inner = pk["0.ff.w2"].K
+    plan = _plan_for(plan, pk, compact=False, tokens=M, C=C, inner=inner, L=L, latent_dim=latent.shape[-1])
     sf, pf = ops.token_features(latent.reshape(n, L, -1).contiguous(), xyz.reshape(n, L, 3).contiguous(),
                                 scale.reshape(n).contiguous(), x.reshape(n, 7).contiguous())
     shape_emb = ops.linear(sf, pk["shape.w"], pk["shape.b"])
@@ -372,17 +441,12 @@ def denoiser_forward(pk, x, timesteps, latent, xyz, part_valids, scale, ref_part
     # In the split-f16 mode the GEMM inputs produced by our own kernels (normalised rows, attention
     # outputs, GEGLU activations) travel as pre-split fp16 planes: the big GEMMs then do no conversions.
     split = ops.split_mode()
-    inner = pk[f"0.ff.w2"].K
     if split:
         norm, att, u = (ops.SplitAct.empty(M, C, h.device), ops.SplitAct.empty(M, C, h.device),
                         ops.SplitAct.empty(M, inner, h.device))
     else:
         norm, att, u = torch.empty_like(h), torch.empty_like(h), None
-    # lab switch (PFPP_EVAL_WD_FULL=1): qkv / out-projection / second feed-forward linear through csrc/gemm_wd.hip (bit-identical).  With
-    # all 640 slots evaluated (16,000 tokens) the 256 x 128 tiled kernel has enough tiles per CU that its LDS traffic is not the bound:
-    # 6.756 vs 6.751 ms per sampler step (profiles/r04zw_ab_wd_full.txt) — off by default
-    wd = (split and not ops.SINGLE_PASS and capture is None and C % 128 == 0 and inner % 64 == 0
-          and os.environ.get("PFPP_EVAL_WD_FULL", "0") == "1")
+    wd = plan.blocks is EvalBlocks.PY_WD
 
     def lin_res(a_, wkey, bkey, K_):
         if wd:
@@ -405,7 +469,8 @@ def denoiser_forward(pk, x, timesteps, latent, xyz, part_valids, scale, ref_part
             capture[f"layer{i}"] = h.clone()
     pooled = ops.mean_pool(h, n, L)
     out = torch.empty((n, 7), dtype=torch.float32, device=h.device)
-    if _fused_heads(pk, pooled, out):
+    if plan.heads_fused:
+        _fused_heads(pk, pooled, out)
         return out.view(B, P, 7)
     for name, c0, width in (("mlp_out_trans", 0, 3), ("mlp_out_rot", 3, 4)):
         v = ops.linear(pooled, pk[f"{name}.0.w"], pk[f"{name}.0.b"], act="silu")

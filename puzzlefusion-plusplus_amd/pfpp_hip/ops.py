@@ -315,7 +315,12 @@ def split_mode() -> bool:
     pre-split fp16 planes — same bytes as fp32.  The consuming GEMM is then the LDS-DMA staged plane kernel
     (csrc/gemm_pl.hip: no staging registers, no conversions, no ds_write in its K loop), bit-identical to the
     register-staged kernel and 1.3-1.6x faster on the 3,850-row shapes.  PFPP_SPLIT_ACT=0 restores fp32 activations."""
-    return GEMM_MODE == "f16x3" and _os.environ.get("PFPP_SPLIT_ACT", "1") == "1"
+    return GEMM_MODE == "f16x3" and split_act()
+
+
+def split_act() -> bool:
+    """PFPP_SPLIT_ACT (default 1) alone: what split_mode() adds to the GEMM mode"""
+    return _os.environ.get("PFPP_SPLIT_ACT", "1") == "1"
 
 
 # When set to a list, every pfpp_gemm launch appends (start_event, end_event, flops, kernel_name):
@@ -919,9 +924,10 @@ def embed_tokens_small(latent: torch.Tensor, xyz: torch.Tensor, scale: torch.Ten
 
 
 def gemm_small(a, w, *, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """a . w^T (+ bias) (+ residual) for few rows (pfpp_gemm_small): a = SplitAct planes [M, K], w = packing.PW [N, K] (its
-    fragment-blocked planes are built on first use); out may be the residual tensor"""
+               out: Optional[torch.Tensor] = None, variant: int = 0) -> torch.Tensor:
+    """a . w^T (+ bias) (+ residual) for few rows (pfpp_gemm_small_v): a = SplitAct planes [M, K], w = packing.PW [N, K] (its
+    fragment-blocked planes are built on first use); out may be the residual tensor.  variant: 0 = the library's choice of kernel,
+    1 = the one-chain kernel at every shape (the cross-check of the split-contraction kernel)"""
     from ._lib import PlanesC, PwC
 
     M, K = a.hi.shape
@@ -935,24 +941,10 @@ def gemm_small(a, w, *, bias: Optional[torch.Tensor] = None, residual: Optional[
     if out is None:
         out = torch.empty((M, w.N), dtype=torch.float32, device=a.hi.device)
     ap = PlanesC(a.hi.data_ptr(), a.lo.data_ptr(), 1.0)
-    check(_lib.load().pfpp_gemm_small(C.byref(ap), a.hi.stride(0), C.byref(pw), _ptr(bias), _ptr(residual),
-                                      0 if residual is None else residual.stride(0), _ptr(out), out.stride(0), M, w.N, K, _stream()),
-          "pfpp_gemm_small")
+    check(_lib.load().pfpp_gemm_small_v(C.byref(ap), a.hi.stride(0), C.byref(pw), _ptr(bias), _ptr(residual),
+                                        0 if residual is None else residual.stride(0), _ptr(out), out.stride(0), M, w.N, K, variant,
+                                        _stream()), "pfpp_gemm_small")
     return out
-
-
-WD_PF = _os.environ.get("PFPP_WD_PF", "0") == "1"          # lab: the software-pipelined loop of csrc/gemm_wd.hip (off by default)
-
-
-def wd_kernel_name(big: bool, single_pass: bool = False, shape=None) -> str:
-    """the instantiation pfpp_gemm_wd / pfpp_gemm_wd_f16 launch (csrc/gemm_wd.hip gemm_wd_impl: tile by shape, X1 = single pass; the
-    software-pipelined loop from 512 small tiles up — shape = (M, N, K)), spelled as rocprofv3 prints it — bench.py looks the counter
-    traffic of the dominant kernel up under this name"""
-    if not big and not single_pass and shape is not None and WD_PF:
-        M, N, K = shape
-        if ((M + 63) // 64) * (N // 128) >= 512 and K >= 224:
-            return "gemm_wd_pf_kernel<2, 1, 4>"
-    return "gemm_wd_kernel<%s, %s>" % ("4, 2, 4" if big else "2, 1, 3", "true" if single_pass else "false")
 
 
 def gemm_wd(a, w, *, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
@@ -982,8 +974,7 @@ def gemm_wd(a, w, *, bias: Optional[torch.Tensor] = None, residual: Optional[tor
              0 if residual is None else residual.stride(0), _ptr(out), out.stride(0), M, w.N, K, _stream()), "pfpp_gemm_wd")
     if ev is not None:
         ev[1].record()
-        big = w.N % 256 == 0 and ((M + 127) // 128) * (w.N // 256) >= 240
-        GEMM_TRACE.append((ev[0], ev[1], 2.0 * M * w.N * K, wd_kernel_name(big, single_pass, (M, w.N, K)), (M, w.N, K, 1, "none", 0)))
+        GEMM_TRACE.append((ev[0], ev[1], 2.0 * M * w.N * K, _lib.load().pfpp_last_gemm_kernel().decode(), (M, w.N, K, 1, "none", 0)))
     return out
 
 

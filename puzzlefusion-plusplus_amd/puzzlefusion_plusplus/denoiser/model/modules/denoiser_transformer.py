@@ -81,9 +81,10 @@ class DenoiserTransformer(nn.Module):
             object.__setattr__(self, "_engine", DenoiserTrainEngine(self))
         return self._engine
 
-    def forward(self, x, timesteps, latent, xyz, part_valids, scale, ref_part, layout=None):
+    def forward(self, x, timesteps, latent, xyz, part_valids, scale, ref_part, layout=None, plan=None):
         """x [B,P,7], timesteps i64 [B], latent [B,P,L,64], xyz [B,P,L,3], part_valids [B,P],
-        scale [B,P,1], ref_part bool [B,P] -> predicted noise [B,P,7] (trans 3 | rot 4)"""
+        scale [B,P,1], ref_part bool [B,P] -> predicted noise [B,P,7] (trans 3 | rot 4).
+        plan (eval mode only): a pfpp_hip.denoiser.EvalPlan naming the kernels of the step; None = the library's choice"""
         if self.training and torch.is_grad_enabled():
             # train mode (dropouts active) with gradients: the fused training engine behind autograd
             eng = self.train_engine()
@@ -98,6 +99,6 @@ class DenoiserTransformer(nn.Module):
             # free of device->host reads: required inside HIP-graph capture
             return hip_denoiser.denoiser_forward_compact(self.packed(), x.float(), timesteps, latent, xyz, part_valids, scale,
                                                          ref_part, num_layers=self.num_layers, num_heads=self.num_heads,
-                                                         layout=layout)
+                                                         layout=layout, plan=plan)
         return hip_denoiser.denoiser_forward(self.packed(), x.float(), timesteps, latent, xyz, part_valids, scale, ref_part,
-                                             num_layers=self.num_layers, num_heads=self.num_heads)
+                                             num_layers=self.num_layers, num_heads=self.num_heads, plan=plan)

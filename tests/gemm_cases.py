@@ -721,10 +721,12 @@ def tile_of(kernel: str):
         return 32 * int(f[0]) * int(f[3]), 32 * int(f[1]) * int(f[4])          # <MT, NT, WPRE, WM, WN, ...>
     if name == "gemm_f32_mfma_kernel":
         return 64 * int(f[0]), 64 * int(f[1])
-    if name in ("gemm_wd_kernel", "gemm_wd_pf_kernel"):
+    if name == "gemm_wd_kernel":
         return 32 * int(f[0]), 128 * int(f[1])
     if name == "gemm_small_kernel":
         return 32, 128
+    if name == "gemm_small_ks_kernel":
+        return 32, 32                                                          # its grid: one workgroup per 32 x 32 output unit
     raise ValueError(f"no tile known for kernel {kernel!r}")
 
 
@@ -1031,7 +1033,7 @@ def run_wd(c: Case, dev):
         Af = P.Planes(shifted("a_hi", M), shifted("a_lo", M))
         Wf = P.Planes(shifted("w_hi", K), shifted("w_lo", K))
         P.gemm_wd(Af, Wf, out, M=M, N=N, K=K, bias=bias, residual=res, transposed=True)
-        kernel = ops.wd_kernel_name(False, False, (M, N, K))
+        kernel = _last_kernel()
         P.gemm(P.Planes(d.t["a_hi"], d.t["a_lo"]), P.Planes(d.t["w_hi"], d.t["w_lo"]), twin, M=M, N=N, K=K, w_kmajor=True, bias=bias,
                residual=twin if res is not None else None, splits=1, lda=d.buf("a_hi").ld, ldw=d.buf("w_hi").ld, ldc=ob.ld, ldr=ob.ld,
                a_off=d.buf("a_hi").off, w_off=d.buf("w_hi").off, c_off=ob.off, r_off=ob.off)
@@ -1042,11 +1044,10 @@ def run_wd(c: Case, dev):
         pw = PW(b["extra"]["w_pw"].to(dev))
         if kind == "small":
             ops.gemm_small(a, pw, bias=bias, residual=res, out=out)
-            kernel = "gemm_small_kernel"
+            kernel = _last_kernel()
         else:
             ops.gemm_wd(a, pw, bias=bias, residual=res, out=out, single_pass=kind == "f16")
-            big = N % 256 == 0 and ((M + 127) // 128) * (N // 256) >= 240      # (gemm_wd_impl's tile rule, as ops.gemm_wd restates it)
-            kernel = ops.wd_kernel_name(big, kind == "f16", (M, N, K))
+            kernel = _last_kernel()
             prev = ops.SINGLE_PASS
             try:
                 ops.SINGLE_PASS = kind == "f16"

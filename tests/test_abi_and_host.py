@@ -569,4 +569,4 @@ def test_library_never_touches_a_register_with_an_lds_read_in_flight(hip_lib, tm
         for k, moves in scanner.moves_of_loaded_registers(text.splitlines(True), "gemm_wd_").items():
             n_wd += 1
             assert not moves, (scanner.demangle(k)[:100], moves[:4])
-    assert n_kernels > 100 and n_reads > 500 and n_wd >= 5          # it really was the kernels' code that was scanned
+    assert n_kernels > 100 and n_reads > 500 and n_wd == 4          # it really was the kernels' code that was scanned (all four gemm_wd_kernel instantiations)

@@ -24,15 +24,14 @@ def load_cases():
 
 
 gc = load_cases()
-KERNELS = {}               # case -> pfpp_last_gemm_kernel() of its launch, groups A to F (the coverage test reads it)
+KERNELS = {}               # case -> pfpp_last_gemm_kernel() of its launch (the coverage test reads it)
 
 
 def _run(dev, name):
     c = gc.CASES[name]
     rep, flags = gc.run(c, dev)
     print(gc.describe(rep))
-    if c.group in "ABCDEF":
-        KERNELS[name] = rep["kernel"]
+    KERNELS[name] = rep["kernel"]
     assert rep["finite"], (name, "non-finite output")
     assert rep["guards_ok"], (name, "a guard row or column of an output was written")
     for tag, band, e, bound in rep["lines"]:
@@ -101,14 +100,15 @@ def test_g_weight_direct_and_few_row_gemm(dev, name):
 
 
 def test_every_pinned_instantiation_ran_against_a_reference(dev):
-    """the kernel names recorded by groups A to F include every distinct expected name of test_gemm_kernel_choice_is_pinned's table:
-    no instantiation is left that is launched by name only"""
+    """the kernel names recorded by groups A to G include every distinct expected name of the tables of
+    test_gemm_kernel_choice_is_pinned and test_wd_and_small_kernel_choice_is_pinned: no instantiation is left that is launched by
+    name only"""
     import test_gpu_parity as tgp
 
-    for name in [n for g in "ABCDEF" for n in gc.GROUPS[g]]:      # (a run of this test alone: launch what has not run yet)
+    for name in [n for g in "ABCDEFG" for n in gc.GROUPS[g]]:     # (a run of this test alone: launch what has not run yet)
         if name not in KERNELS:
             rep, _ = gc.run(gc.CASES[name], dev)
             KERNELS[name] = rep["kernel"]
-    want = {k for _, k in tgp._gemm_choice_cases().values()}
+    want = {k for _, k in tgp._gemm_choice_cases().values()} | {k for _, k in tgp._wd_small_choice_cases().values()}
     missing = sorted(want - set(KERNELS.values()))
     assert not missing, missing

@@ -90,39 +90,6 @@ def test_ball_query_bit_exact_vs_oracle(dev, oracle_lib, N, S, r, ns):
     assert torch.equal(got.cpu().long(), want)
 
 
-def test_gemm_wd_pipelined_loop_is_bit_identical_too(dev):
-    """the lab form of csrc/gemm_wd.hip (PFPP_WD_PF=1, read once per process: hence a fresh interpreter): next tile's fragments read while
-    the current one is multiplied, one memory instruction in the shadow of every matrix instruction — same products in the same order:
-    bit-identical to the tiled GEMM at 7, 8, 11, 16 and 17 K-tiles, ragged last row tile included"""
-    import os
-    import subprocess
-    import sys
-    from pathlib import Path
-
-    root = Path(__file__).resolve().parents[1]
-    code = r"""
-import math, sys, torch
-sys.path.insert(0, r"%s")
-from pfpp_hip import ops, planes as P
-from pfpp_hip.packing import PW
-dev = torch.device("cuda:0")
-for M, N, K in ((3850, 1536, 224), (3850, 1536, 256), (3850, 1536, 352), (3850, 1536, 512), (4100, 1024, 544), (16000, 512, 512)):
-    g = torch.Generator().manual_seed(M + N + K)
-    pl = P.split(torch.randn(M, K, generator=g).to(dev))
-    a = ops.SplitAct(pl.hi, pl.lo)
-    pw = PW((torch.randn(N, K, generator=g) / math.sqrt(K)).to(dev).contiguous())
-    bias = torch.randn(N, generator=g).to(dev) * 0.1
-    res = torch.randn(M, N, generator=g).to(dev)
-    assert ops.wd_kernel_name(False, False, (M, N, K)) == "gemm_wd_pf_kernel<2, 1, 4>"
-    out = res.clone(); ops.gemm_wd(a, pw, bias=bias, residual=out, out=out)
-    tiled = res.clone(); ops.gemm(a, pw, M=M, N=N, K=K, lda=K, out=tiled, ldc=N, bias=bias, residual=tiled, ldr=N)
-    assert torch.equal(out, tiled), (M, N, K)
-print("pipelined loop: bit-identical")
-""" % str(root / "puzzlefusion-plusplus_amd")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, PFPP_WD_PF="1"))
-    assert r.returncode == 0 and "bit-identical" in r.stdout, r.stderr[-2000:]
-
-
 @pytest.mark.parametrize("N,S,F", [(1024, 256, 16), (512, 256, 8)])
 def test_sampling_chain_is_exact_next_to_a_gemm_on_another_stream(dev, oracle_lib, N, S, F):
     """Round 5: pfpp_fps + pfpp_ball_query of one input, launch after launch, while a second stream of the process runs a
@@ -1402,12 +1369,14 @@ def test_fp16_mfma_joint_step_configs4_vs_f16x3(dev):
 
 
 @pytest.mark.parametrize("parts", [(1,), (8,), (20,), (3, 7), (2, 2, 5, 1)])
-def test_small_puzzle_forward_fused_heads_equal_layerwise(weights_sd, dev, parts, monkeypatch):
+def test_small_puzzle_forward_fused_heads_equal_layerwise(weights_sd, dev, parts):
     """one puzzle in flight (1 .. 20 fragments = 25 .. 500 tokens, and several short puzzles in one call): the eval forward with the
     pool -> both-heads kernel (csrc/heads.hip, one launch for 1 .. 20 rows of a 32-row block) against the layer-wise head GEMMs
-    (PFPP_HEADS_FUSED=0) on the same inputs — predicted noise within 1e-5 (same split-f16 contraction; the last 3- / 4-column layer
+    (an EvalPlan with heads_fused = False) on the same inputs — predicted noise within 1e-5 (same split-f16 contraction; the last 3- / 4-column layer
     is fp32 FMAs instead of a split-f16 GEMM), deterministic, padded slots exactly zero."""
-    from pfpp_hip import config
+    import dataclasses
+
+    from pfpp_hip import config, denoiser as D, ops
     from puzzlefusion_plusplus.denoiser.model.modules.denoiser_transformer import DenoiserTransformer
 
     m = DenoiserTransformer(config.denoiser_config())
@@ -1427,10 +1396,12 @@ def test_small_puzzle_forward_fused_heads_equal_layerwise(weights_sd, dev, parts
     ref[:, 0] = True
     ts = torch.randint(0, 1000, (B,), generator=gen).to(dev)
     valid_d, ref_d = valid.to(dev), ref.to(dev)
-    monkeypatch.setenv("PFPP_HEADS_FUSED", "0")
+    facts = dict(gemm_mode=ops.GEMM_MODE, split_act=ops.split_act(), single_pass=ops.SINGLE_PASS, traced=False, C=512,
+                 inner=m.packed()["0.ff.w2"].K, L=25, latent_dim=64, embed_packed=True)
+    default = D.choose_eval(compact=True, tokens=25 * sum(parts), **facts)
+    assert default.heads_fused
     with torch.no_grad():
-        want = m(x, ts, latent, xyz, valid_d, scale, ref_d)
-    monkeypatch.setenv("PFPP_HEADS_FUSED", "1")
+        want = m(x, ts, latent, xyz, valid_d, scale, ref_d, plan=dataclasses.replace(default, heads_fused=False))
     with torch.no_grad():
         got = [m(x, ts, latent, xyz, valid_d, scale, ref_d) for _ in range(3)]
     torch.cuda.synchronize()
@@ -1441,10 +1412,10 @@ def test_small_puzzle_forward_fused_heads_equal_layerwise(weights_sd, dev, parts
     assert float(got[0][~v].abs().max() if (~v).any() else 0.0) == 0.0
     # all slots evaluated (the reference's form): same bound
     m.compact_padded = False
-    monkeypatch.setenv("PFPP_HEADS_FUSED", "0")
+    default_all = D.choose_eval(compact=False, tokens=B * 20 * 25, **facts)
+    assert default_all.heads_fused
     with torch.no_grad():
-        want_all = m(x, ts, latent, xyz, valid_d, scale, ref_d)
-    monkeypatch.setenv("PFPP_HEADS_FUSED", "1")
+        want_all = m(x, ts, latent, xyz, valid_d, scale, ref_d, plan=dataclasses.replace(default_all, heads_fused=False))
     with torch.no_grad():
         got_all = m(x, ts, latent, xyz, valid_d, scale, ref_d)
     assert (got_all - want_all).abs().max() <= 1e-5 * max(1.0, float(want_all.abs().max()))
@@ -1535,7 +1506,7 @@ def test_token_embedding_in_one_launch_equals_the_four_launch_path(weights_sd, d
 
 
 @pytest.mark.parametrize("M,N,K", [(25, 512, 512), (125, 512, 2048), (500, 512, 512), (333, 1536, 1024), (1, 128, 512), (2000, 512, 2048), (512, 512, 2048), (37, 1536, 2048)])
-def test_gemm_small_vs_float64_and_the_tiled_gemm(dev, M, N, K, monkeypatch):
+def test_gemm_small_vs_float64_and_the_tiled_gemm(dev, M, N, K):
     """csrc/gemm_small.hip (out-projections / second feed-forward linear of a few-token step): A planes . fragment-blocked weight planes
     + bias + residual, in place — against float64 of the values the planes stand for, against the tiled plane GEMM it replaces
     (same products, another association), and deterministic"""
@@ -1570,10 +1541,8 @@ def test_gemm_small_vs_float64_and_the_tiled_gemm(dev, M, N, K, monkeypatch):
     ops.gemm_small(a, pw, bias=bias, residual=again, out=again)
     assert torch.equal(again, out)
     # round 6: K = 2048 at <= 512 rows runs with the contraction split over eight waves (gemm_small_ks_kernel); the one-chain kernel agrees
-    monkeypatch.setenv("PFPP_GEMM_SMALL_KS", "0")
     chain = res.clone()
-    ops.gemm_small(a, pw, bias=bias, residual=chain, out=chain)
-    monkeypatch.delenv("PFPP_GEMM_SMALL_KS")
+    ops.gemm_small(a, pw, bias=bias, residual=chain, out=chain, variant=1)
     assert float((out - chain).abs().max() / chain.abs().max()) < 2e-6
     assert (K == 2048 and M <= 512) or torch.equal(out, chain)
     plain = ops.gemm_small(a, pw)                                        # no bias, no residual, fresh output
@@ -1650,11 +1619,13 @@ def test_reblock_planes_equals_the_host_side_fragment_blocking(dev, N, K):
 
 
 @pytest.mark.parametrize("parts", [(5,), (20, 3, 11), (2,) * 16])
-def test_eval_blocks_sequenced_from_c_are_bit_identical(weights_sd, dev, parts, monkeypatch):
+def test_eval_blocks_sequenced_from_c_are_bit_identical(weights_sd, dev, parts):
     """pfpp_tlayers_eval (csrc/tlayer.hip): the compact eval forward's six blocks enqueued from one C call are the same launches with
-    the same arguments as the Python sequence (PFPP_EVAL_CSEQ=0) — predicted noise bit-identical, for one puzzle in flight and for
+    the same arguments as the Python sequence (an EvalPlan with blocks = PY_TILED) — predicted noise bit-identical, for one puzzle in flight and for
     ragged batches, in the parity arithmetic and in the single-pass fp16 mode"""
-    from pfpp_hip import config, ops
+    import dataclasses
+
+    from pfpp_hip import config, denoiser as D, ops
     from puzzlefusion_plusplus.denoiser.model.modules.denoiser_transformer import DenoiserTransformer
 
     m = DenoiserTransformer(config.denoiser_config())
@@ -1679,14 +1650,16 @@ def test_eval_blocks_sequenced_from_c_are_bit_identical(weights_sd, dev, parts, 
         for sp in (False, True):
             ops.SINGLE_PASS = sp
             outs = []
-            monkeypatch.setenv("PFPP_EVAL_LNLIN_ROWS", "0")          # same launches as the Python sequence
-            for flag in ("0", "1"):
-                monkeypatch.setenv("PFPP_EVAL_CSEQ", flag)
+            default = D.choose_eval(compact=True, gemm_mode=ops.GEMM_MODE, split_act=ops.split_act(), single_pass=sp, traced=False,
+                                    tokens=25 * sum(parts), C=512, inner=m.packed()["0.ff.w2"].K, L=25, latent_dim=64, embed_packed=True)
+            assert default.blocks is D.EvalBlocks.C_SEQUENCED and default.lnlin_max_rows == 2048
+            # no few-token kernel anywhere (the embedding neither): same launches as the Python sequence
+            for blocks in (D.EvalBlocks.PY_TILED, D.EvalBlocks.C_SEQUENCED):
                 with torch.no_grad():
-                    outs.append(m(x, ts, latent, xyz, valid_d, scale, ref_d))
+                    outs.append(m(x, ts, latent, xyz, valid_d, scale, ref_d,
+                                  plan=dataclasses.replace(default, lnlin_max_rows=0, embed_fused=False, blocks=blocks)))
             # default: for <= 512 tokens the LayerNorms ride in the GEMMs that consume them (csrc/lnlin_small.hip): same LayerNorm
             # bits, another summation order in the contraction -> equal to fp32 rounding, and deterministic
-            monkeypatch.setenv("PFPP_EVAL_LNLIN_ROWS", "2048")
             with torch.no_grad():
                 fused = [m(x, ts, latent, xyz, valid_d, scale, ref_d) for _ in range(2)]
             torch.cuda.synchronize()
@@ -2155,6 +2128,60 @@ def test_gemm_kernel_choice_is_pinned(dev, case):
     from pfpp_hip import _lib
 
     call, want = _gemm_choice_cases()[case]
+    call(dev)
+    torch.cuda.synchronize()
+    assert _lib.load().pfpp_last_gemm_kernel().decode() == want
+
+
+def _wd_small_choice_cases():
+    """name -> (call(dev), expected pfpp_last_gemm_kernel()).  One pfpp_gemm_wd / pfpp_gemm_wd_f16 / pfpp_gemm_small_v launch per case,
+    at the smallest depth each entry accepts (32 / 512 / 2048: the choice of pfpp_gemm_small reads the depth)."""
+    import math
+
+    from pfpp_hip import ops, planes as P
+    from pfpp_hip.packing import PW
+
+    def operands(dev, M, N, K):
+        pl = P.split(torch.randn(M, K, device=dev))
+        return ops.SplitAct(pl.hi, pl.lo), PW(torch.randn(N, K, device=dev) / math.sqrt(K))
+
+    def wd(M, N, single_pass=False):
+        def call(dev):
+            a, w = operands(dev, M, N, 32)
+            ops.gemm_wd(a, w, single_pass=single_pass)
+        return call
+
+    def small(M, K, variant=0):
+        def call(dev):
+            a, w = operands(dev, M, 32, K)
+            ops.gemm_small(a, w, variant=variant)
+        return call
+
+    return {
+        # ---- pfpp_gemm_wd: the 128 x 256 tile from WD_BIG_MIN_TILES = 240 such tiles up where N % 256 == 0 (239 x 128 = 30,592 rows)
+        "wd_239_big_tiles": (wd(30592, 256), "gemm_wd_kernel<2, 1, 3, false>"),
+        "wd_240_big_tiles": (wd(30593, 256), "gemm_wd_kernel<4, 2, 4, false>"),
+        "wd_n384": (wd(40000, 384), "gemm_wd_kernel<2, 1, 3, false>"),
+        "wd_f16_239_big_tiles": (wd(30592, 256, single_pass=True), "gemm_wd_kernel<2, 1, 3, true>"),
+        "wd_f16_240_big_tiles": (wd(30593, 256, single_pass=True), "gemm_wd_kernel<4, 2, 4, true>"),
+        # ---- pfpp_gemm_small: the contraction split over the waves at K = SMALL_KS_K = 2048 up to SMALL_KS_MAX_ROWS = 512 rows
+        "small_k2048_m512": (small(512, 2048), "gemm_small_ks_kernel<8, 2>"),
+        "small_k2048_m513": (small(513, 2048), "gemm_small_kernel"),
+        "small_k512_m33": (small(33, 512), "gemm_small_kernel"),
+        "small_k2048_m512_variant1": (small(512, 2048, variant=1), "gemm_small_kernel"),
+    }
+
+
+@pytest.mark.parametrize("case", sorted(_wd_small_choice_cases()))
+def test_wd_and_small_kernel_choice_is_pinned(dev, case):
+    """The two GEMMs of the eval / sampler step pick their kernel from the call's sizes, the arithmetic and (pfpp_gemm_small_v) the
+    variant argument alone; this pins the pick on both sides of both thresholds, one launch per case.  The expected names are the
+    kernels rocprofv3 recorded for these calls at the commit before the selection became a pure function
+    (profiles/eval_choice_parent_per_case.txt: name, grid and block per case; the variant = 1 case was traced there with
+    the environment switch that the argument replaces)."""
+    from pfpp_hip import _lib
+
+    call, want = _wd_small_choice_cases()[case]
     call(dev)
     torch.cuda.synchronize()
     assert _lib.load().pfpp_last_gemm_kernel().decode() == want
