@@ -617,6 +617,22 @@ int pfpp_pose_apply_points(const float* pts, const int32_t* pose_idx, const floa
 int pfpp_edge_histogram(const float* pts, const int32_t* idx_a, const int32_t* idx_b,
                         const int32_t* edge_off, int32_t* hist, int64_t n_edges, int64_t max_m,
                         pfpp_stream_t stream);
+/* pfpp_edge_features_batch: the verifier input of several puzzles of a pfpp_match_edges batch in one launch:
+ * get_distance_for_matching_pts (utils/node_merge_utils.py:62-89), _make_cd_to_bins (auto_aggl.py:385-389), the scatter
+ * into the upper triangle and the normalisation (auto_aggl.py:193-201).  T = P (P - 1) / 2 slots per puzzle.
+ * pts [total_points, 3] = the transformed by-area points of the whole batch, puzzle b from point pt_off[b] (int64 [B]);
+ * idx_a, idx_b (point indices within the puzzle), row_off int64 [B + 1] and edge_off int32 [B, T + 1] exactly as
+ * pfpp_match_edges takes and writes them (a slot's rows are row_off[b] + [edge_off[b, s], edge_off[b, s + 1])); puz int32 [nb] =
+ * the puzzles of this call, each in [0, B), in any order; out float32 [nb, T, 7].
+ * Per (puzzle, slot): pfpp_edge_histogram's six counts h (the same device function: (dx dx + dy dy) + dz dz, fminf, fa + fb,
+ * the same thresholds, d >= 100 dropped), then out = (h / max(sum h, 1) in fp32, sum h): bit for bit what the per-puzzle route
+ * (pfpp_edge_histogram, index_put by triangle position, normalise_edge_hist) gives.  A slot without rows is seven zeros; every
+ * slot of every listed puzzle is written.  No float atomics: the result depends neither on the grid nor on the other puzzles of
+ * the call.  An entry of puz outside [0, B), or a slot with more than max_m rows, is written as zeros and reads nothing.
+ * PFPP_EUNSUPPORTED before any launch for P > 32, max_m > 6000 or more than 65535 puzzles; nb = 0 does nothing.  */
+int pfpp_edge_features_batch(const float* pts, const int64_t* pt_off, const int32_t* idx_a, const int32_t* idx_b,
+                             const int64_t* row_off, const int32_t* edge_off, const int32_t* puz, float* out,
+                             int64_t nb, int64_t B, int64_t P, int64_t max_m, pfpp_stream_t stream);
 
 /* ---- 8f-4: GPU-side augmentation of GeometryLatentDataset.__getitem__ (denoiser/dataset/dataset.py:165-215) ---
  * For a batch of stored puzzles part_pcs_gt [B,P,N,3] (assembled frame, padded): rotate the whole assembly by

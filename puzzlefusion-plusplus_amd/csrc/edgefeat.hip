@@ -40,22 +40,16 @@ __global__ __launch_bounds__(256) void pose_apply_points_kernel(const float* __r
   out[3 * i + 2] = rz + ps[2];
 }
 
-__global__ __launch_bounds__(256) void edge_histogram_kernel(const float* __restrict__ pts,
-                                                             const int32_t* __restrict__ idx_a,
-                                                             const int32_t* __restrict__ idx_b,
-                                                             const int32_t* __restrict__ edge_off,
-                                                             int32_t* __restrict__ hist, int max_m) {
-  extern __shared__ __align__(16) float eh_smem[];
-  float* a = eh_smem;                 // [3*max_m]
-  float* b = eh_smem + 3 * max_m;     // [3*max_m]
-  __shared__ int s_hist[6];
-  const int e = blockIdx.x;
-  const int o = edge_off[e];
-  const int m = edge_off[e + 1] - o;
+// The per-edge body both histogram kernels share: the matched points of the edge (rows [o, o + m) of idx_a / idx_b, indices into
+// pts) are staged in LDS, every thread takes the rows tid, tid + 256, ... and counts d = fa + fb into s_hist (integer LDS atomics:
+// the result does not depend on the order).  s_hist must be zeroed by the caller's threads 0..5 before the call (the first barrier
+// in here orders that); it is complete for every thread on return.
+__device__ __forceinline__ void edge_hist_body(const float* __restrict__ pts, const int32_t* __restrict__ idx_a,
+                                               const int32_t* __restrict__ idx_b, int64_t o, int m, float* __restrict__ a,
+                                               float* __restrict__ b, int* s_hist) {
   const int tid = threadIdx.x;
-  if (tid < 6) s_hist[tid] = 0;
   for (int i = tid; i < m; i += 256) {
-    const int ia = idx_a[o + i], ib = idx_b[o + i];
+    const int64_t ia = idx_a[o + i], ib = idx_b[o + i];
     a[3 * i] = pts[3 * ia]; a[3 * i + 1] = pts[3 * ia + 1]; a[3 * i + 2] = pts[3 * ia + 2];
     b[3 * i] = pts[3 * ib]; b[3 * i + 1] = pts[3 * ib + 1]; b[3 * i + 2] = pts[3 * ib + 2];
   }
@@ -83,7 +77,62 @@ __global__ __launch_bounds__(256) void edge_histogram_kernel(const float* __rest
     if (bin >= 0) atomicAdd(&s_hist[bin], 1);
   }
   __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void edge_histogram_kernel(const float* __restrict__ pts,
+                                                             const int32_t* __restrict__ idx_a,
+                                                             const int32_t* __restrict__ idx_b,
+                                                             const int32_t* __restrict__ edge_off,
+                                                             int32_t* __restrict__ hist, int max_m) {
+  extern __shared__ __align__(16) float eh_smem[];
+  float* a = eh_smem;                 // [3*max_m]
+  float* b = eh_smem + 3 * max_m;     // [3*max_m]
+  __shared__ int s_hist[6];
+  const int e = blockIdx.x;
+  const int o = edge_off[e];
+  const int m = edge_off[e + 1] - o;
+  const int tid = threadIdx.x;
+  if (tid < 6) s_hist[tid] = 0;
+  edge_hist_body(pts, idx_a, idx_b, o, m, a, b, s_hist);
   if (tid < 6) hist[e * 6 + tid] = s_hist[tid];
+}
+
+// Workgroup (s, k): slot s of puzzle puz[k] of a pfpp_match_edges batch -> out[k, s, 0..7): the histogram of the slot's rows, then
+// normalise_edge_hist's arithmetic (the counts are small integers, exact in fp32; one correctly rounded fp32 division each).
+// A puzzle index outside [0, B) or a slot whose row count lies outside [0, max_m] (what the LDS was sized for) is written as seven
+// zeros and reads nothing.
+__global__ __launch_bounds__(256) void edge_features_batch_kernel(const float* __restrict__ pts, const int64_t* __restrict__ pt_off,
+                                                                  const int32_t* __restrict__ idx_a,
+                                                                  const int32_t* __restrict__ idx_b,
+                                                                  const int64_t* __restrict__ row_off,
+                                                                  const int32_t* __restrict__ edge_off,
+                                                                  const int32_t* __restrict__ puz, float* __restrict__ out, int B,
+                                                                  int T, int max_m) {
+  extern __shared__ __align__(16) float eh_smem[];
+  float* a = eh_smem;
+  float* b = eh_smem + 3 * max_m;
+  __shared__ int s_hist[6];
+  const int s = blockIdx.x, k = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int p = puz[k];
+  float* o7 = out + ((int64_t)k * T + s) * 7;
+  int m = -1;
+  int64_t o = 0;
+  if (p >= 0 && p < B) {
+    const int32_t* eo = edge_off + (int64_t)p * (T + 1) + s;
+    m = eo[1] - eo[0];
+    o = row_off[p] + eo[0];
+  }
+  if (m < 0 || m > max_m) {            // uniform over the workgroup
+    if (tid < 7) o7[tid] = 0.0f;
+    return;
+  }
+  if (tid < 6) s_hist[tid] = 0;
+  edge_hist_body(pts + 3 * pt_off[p], idx_a, idx_b, o, m, a, b, s_hist);
+  if (tid < 7) {
+    const int cnt = ((((s_hist[0] + s_hist[1]) + s_hist[2]) + s_hist[3]) + s_hist[4]) + s_hist[5];
+    o7[tid] = tid < 6 ? (float)s_hist[tid] / (float)(cnt == 0 ? 1 : cnt) : (float)cnt;
+  }
 }
 
 }  // namespace
@@ -107,5 +156,22 @@ extern "C" int pfpp_edge_histogram(const float* pts, const int32_t* idx_a, const
   (void)pfpp_allow_dyn_lds<edge_histogram_kernel>(6 * 6000 * 4);
   hipLaunchKernelGGL(edge_histogram_kernel, dim3((unsigned)n_edges), dim3(256), smem, pfpp::as_stream(stream), pts,
                      idx_a, idx_b, edge_off, hist, (int)max_m);
+  return pfpp::check_launch(__func__);
+}
+
+extern "C" int pfpp_edge_features_batch(const float* pts, const int64_t* pt_off, const int32_t* idx_a, const int32_t* idx_b,
+                                        const int64_t* row_off, const int32_t* edge_off, const int32_t* puz, float* out,
+                                        int64_t nb, int64_t B, int64_t P, int64_t max_m, pfpp_stream_t stream) {
+  PFPP_REQUIRE(pts && pt_off && idx_a && idx_b && row_off && edge_off && puz && out, "null pointer");
+  PFPP_REQUIRE(nb >= 0 && B >= 0 && P >= 1, "negative count");
+  PFPP_SUPPORTED(P <= 32, "more than 32 pieces per puzzle");
+  PFPP_SUPPORTED(max_m >= 0 && max_m <= 6000, "more than 6000 correspondences on one edge");
+  PFPP_SUPPORTED(nb <= 65535 && B <= 65535, "more than 65535 puzzles");
+  const int64_t T = P * (P - 1) / 2;
+  if (nb == 0 || T == 0) return PFPP_OK;
+  const size_t smem = (size_t)6 * (max_m > 0 ? max_m : 1) * sizeof(float);
+  (void)pfpp_allow_dyn_lds<edge_features_batch_kernel>(6 * 6000 * 4);
+  hipLaunchKernelGGL(edge_features_batch_kernel, dim3((unsigned)T, (unsigned)nb), dim3(256), smem, pfpp::as_stream(stream), pts,
+                     pt_off, idx_a, idx_b, row_off, edge_off, puz, out, (int)B, (int)T, (int)max_m);
   return pfpp::check_launch(__func__);
 }

@@ -10,6 +10,8 @@ pair rule is the only reason the matches leave the GPU.  Here:
   flags and the offsets: (2 T + 2) words per puzzle, T = P (P - 1) / 2); no correspondence passes through the host.
 * DeviceMatches.files(b): what match_edges returns, for the file.  DeviceMatches.prepared(b): what prepare_matching returns, as views
   of the kernel's outputs, for AutoAgglomerative (data_dict["matching_prepared"]).
+* DeviceMatches.batch_prepared() -> BatchMatches: the same for the whole batch as one set of tensors (data_dict["matching_batch"] =
+  (object, b)); the loop then builds the verifier input of all its puzzles with one pfpp_edge_features_batch launch.
 * pack_matches_reference: the kernel's output arrays in numpy, built from match_edges and prepare_matching: the parity target.
 * match_edges_launch: the entry on caller-allocated tensors (tests place canaries around them).
 """
@@ -160,6 +162,58 @@ class DeviceMatches:
                 "max_m": int((off[slots + 1] - off[slots]).max()) if slots.size else 0,
                 "pairs": [(int(i1), int(i2)) for i1, i2 in self._tri[slots]],
                 "point_part": torch.from_numpy(point_part).to(dev), "pair_pos": sel[:-1]}
+
+    def batch_prepared(self) -> "BatchMatches":
+        """what the assembly loop needs of ALL puzzles of the batch as one set of tensors (data_dict["matching_batch"] = (this, b)):
+        one upload, no tensor work per puzzle; the kernel's outputs are used as they are"""
+        return BatchMatches(self)
+
+
+class BatchMatches:
+    """The matches of a DeviceMatches batch as AutoAgglomerative.test_batch takes them: every puzzle b travels as
+    data_dict["matching_batch"] = (this object, b).
+
+    idx_a, idx_b, edge_off [B, T + 1]: the kernel's outputs (no copy); row_off, pt_off int64 [B + 1]: the puzzles' first rows / first
+    by-area points; point_part int32 [sum N]: the piece of every point; pivot int32 [B, P], arange(P) per puzzle: the loop's pivots
+    (a merge writes them through its puzzle's view); pts float32 [sum N, 3]: the by-area points of the batch in the pieces' current
+    frames (every puzzle's state fills its slice and a merge rewrites it through its view); max_m: the longest slot of the batch.
+    The four index arrays come from ONE upload.  A deep copy is the object itself: a dataset sample that carries it is deep-copied
+    per __getitem__, and the states of one call must share one object."""
+
+    def __init__(self, dm: DeviceMatches):
+        import torch
+
+        dev = dm.idx_a.device
+        B, P, T = dm.B, dm.P, dm.T
+        self.dm, self.B, self.P, self.T = dm, B, P, T
+        n_pcs = np.asarray(dm.n_pcs, dtype=np.int64)
+        self.n_points = n_pcs.sum(1)
+        self.pt_off_host = np.concatenate([[0], np.cumsum(self.n_points)]).astype(np.int64)
+        self.row_off_host = np.ascontiguousarray(dm.row_off, dtype=np.int64)
+        total = int(self.pt_off_host[-1])
+        slot = np.tile(np.arange(P, dtype=np.int32), B)
+        point_part = np.repeat(slot, n_pcs.reshape(-1))
+        # index of a point's pivot in the flat [B P] pivot table
+        point_slot = point_part + np.repeat(np.arange(B, dtype=np.int32) * P, self.n_points)
+        # the int64 offsets first (8-byte aligned), then the int32 arrays: pt_off | row_off | pivot | point_part | point_slot
+        blob = torch.from_numpy(np.concatenate([self.pt_off_host.view(np.int32), self.row_off_host.view(np.int32), slot, point_part,
+                                                point_slot])).to(dev)
+        n64 = 2 * (B + 1)
+        off64 = blob[:2 * n64].view(torch.int64)
+        self.pt_off, self.row_off = off64[:B + 1], off64[B + 1:]
+        self.pivot = blob[2 * n64:2 * n64 + B * P].view(B, P)
+        self.point_part = blob[2 * n64 + B * P:2 * n64 + B * P + total]
+        self.point_slot = blob[2 * n64 + B * P + total:]
+        self.idx_a, self.idx_b, self.edge_off = dm.idx_a, dm.idx_b, dm.edge_off
+        self.max_m = int(np.diff(dm.edge_off_host, axis=1).max()) if T else 0
+        self.pts = torch.zeros((total, 3), dtype=torch.float32, device=dev)
+
+    def __deepcopy__(self, memo):
+        return self
+
+    def points(self, b: int):
+        """puzzle b's slice of pts, [N_b, 3] (a view)"""
+        return self.pts[int(self.pt_off_host[b]):int(self.pt_off_host[b + 1])]
 
 
 def _flat(ts):

@@ -1149,6 +1149,33 @@ def edge_histogram(pts: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, 
     return hist
 
 
+def edge_features_batch(pts: torch.Tensor, pt_off: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, row_off: torch.Tensor,
+                        edge_off: torch.Tensor, puz: torch.Tensor, max_m: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the verifier input [nb, T, 7] of the puzzles `puz` (int32 [nb], each in [0, B)) of a pfpp_match_edges batch in one launch:
+    pts [total_points, 3] the transformed by-area points of the whole batch, pt_off int64 [B] (or longer) the puzzles' first points,
+    idx_a / idx_b / row_off int64 [B + 1] / edge_off int32 [B, T + 1] as the batch holds them.  Bit for bit edge_histogram +
+    the scatter by triangle position + normalise_edge_hist per puzzle."""
+    _chk(pts, torch.float32, "pts"); _chk(pt_off, torch.int64, "pt_off"); _chk(row_off, torch.int64, "row_off")
+    for t, nm in ((idx_a, "idx_a"), (idx_b, "idx_b"), (edge_off, "edge_off"), (puz, "puz")):
+        _chk(t, torch.int32, nm)
+    if edge_off.dim() != 2 or row_off.numel() != edge_off.shape[0] + 1 or pt_off.numel() < edge_off.shape[0]:
+        raise ValueError("edge_features_batch: edge_off [B, T + 1], row_off [B + 1] and pt_off [B] expected")
+    B, T = edge_off.shape[0], edge_off.shape[1] - 1
+    P = int(round((1 + (1 + 8 * T) ** 0.5) / 2))
+    if P * (P - 1) // 2 != T:
+        raise ValueError(f"edge_features_batch: {T} slots per puzzle are not a triangle P (P - 1) / 2")
+    nb = puz.numel()
+    if out is None:
+        out = torch.empty((nb, T, 7), dtype=torch.float32, device=pts.device)
+    else:
+        _chk(out, torch.float32, "out")
+        if out.numel() != nb * T * 7:
+            raise ValueError("edge_features_batch: out must hold [nb, T, 7] values")
+    check(_lib.load().pfpp_edge_features_batch(_ptr(pts), _ptr(pt_off), _ptr(idx_a), _ptr(idx_b), _ptr(row_off), _ptr(edge_off), _ptr(puz),
+                                               _ptr(out), nb, B, P, int(max_m), _stream()), "pfpp_edge_features_batch")
+    return out
+
+
 # --------------------------------------------------------------------------- evaluation metrics (8f-3)
 def nn_dist(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     """src [B,n,3], dst [B,m,3] -> [B,n] squared distance to the nearest neighbour (chamferdist's KNN-1 term)"""

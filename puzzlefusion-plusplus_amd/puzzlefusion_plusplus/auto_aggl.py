@@ -201,7 +201,7 @@ class AutoAgglomerative(LightningModule):
             # edge features per puzzle (ragged matching data), ONE verifier call for all of them, bookkeeping per puzzle
             todo = [st for st in active if not st.finish_if_last(last)]
             if todo:
-                efs = [st.edge_features() for st in todo]
+                efs = self._edge_features(todo)
                 logits = self.verifier(torch.cat(efs, 0).contiguous(), torch.cat([st.edge_indices for st in todo], 0).contiguous(),
                                        torch.cat([st.edge_valids for st in todo], 0))
                 for i, st in enumerate(todo):
@@ -210,6 +210,36 @@ class AutoAgglomerative(LightningModule):
         finals = [self._compose(st.x, st.pivot, st.nodes) for st in states]
         metrics = self._evaluate_many([st.data for st in states], finals, [st.n_nodes for st in states])
         return [st.result(finals[i], {k: v[i:i + 1] for k, v in metrics.items()}) for i, st in enumerate(states)]
+
+    @staticmethod
+    def _edge_features(todo) -> list:
+        """the verifier input [1, T, 7] of every state of `todo`, in its order.  A state without data_dict["matching_batch"] builds
+        its own (edge_features(): its launches per puzzle); the states that share a batch object get theirs from one pose-apply and
+        one pfpp_edge_features_batch launch over that object's tensors, whatever their number."""
+        efs, groups = [None] * len(todo), {}
+        for i, st in enumerate(todo):
+            if st.batch is None:
+                efs[i] = st.edge_features()
+            else:
+                groups.setdefault(id(st.batch), (st.batch, []))[1].append(i)
+        for bo, members in groups.values():
+            sts = [todo[i] for i in members]
+            P, nb = bo.P, len(sts)
+            # one upload: the puzzles of the call | per puzzle of the batch the first pose row of its slot in the call (0 elsewhere)
+            call = np.zeros(nb + bo.B, dtype=np.int32)
+            for k, st in enumerate(sts):
+                call[k] = st.batch_index
+                call[nb + st.batch_index] = k * P
+            call = torch.from_numpy(call).to(bo.pts.device)
+            pose_idx = (bo.pivot + call[nb:, None]).view(-1)[bo.point_slot]
+            x = torch.cat([st.x[0] for st in sts], 0) if nb > 1 else sts[0].x[0].contiguous()
+            pts_t = ops.pose_apply_points(bo.pts, pose_idx, x, normalise=False)
+            ef = ops.edge_features_batch(pts_t, bo.pt_off, bo.idx_a, bo.idx_b, bo.row_off, bo.edge_off, call[:nb], bo.max_m)
+            for k, (i, st) in enumerate(zip(members, sts)):
+                b = st.batch_index
+                st._pts_t = pts_t[int(bo.pt_off_host[b]):int(bo.pt_off_host[b + 1])]
+                efs[i] = ef[k:k + 1]
+        return efs
 
     @staticmethod
     def _batched_compose(active):
@@ -412,15 +442,37 @@ class _PuzzleState:
         # "matching_prepared": prepare_matching's dict built on the device (pfpp_hip.matching_edges.DeviceMatches.prepared): the
         # correspondence lists of the file are then neither needed nor read
         prepared = data_dict.get("matching_prepared")
-        self.have_matching = prepared is not None or "edges" in data_dict
-        self.match = prepared if prepared is not None else model.prepare_matching(data_dict, dev) if self.have_matching else None
-        self.pivot = torch.arange(self.n_nodes, dtype=torch.int32, device=dev)
+        # "matching_batch": (pfpp_hip.matching_edges.BatchMatches, b): the matches of a whole matcher batch as one set of tensors.  The
+        # pivots and the by-area points of this puzzle are then VIEWS into that object's tensors (the merges write through them), and
+        # test_batch builds the verifier input of all such puzzles in one launch (_edge_features)
+        self.batch, self.batch_index = None, None
+        if data_dict.get("matching_batch") is not None:
+            self.batch, self.batch_index = data_dict["matching_batch"][0], int(data_dict["matching_batch"][1])
+            if prepared is not None or "edges" in data_dict:
+                raise ValueError("matching_batch: the puzzle also carries matching_prepared or edges; pass one of them")
+            if self.batch.P != P or not 0 <= self.batch_index < self.batch.B:
+                raise ValueError(f"matching_batch: puzzle {self.batch_index} of a batch of {self.batch.B} with P = {self.batch.P}; the loop's P is {P}")
+        self.have_matching = prepared is not None or "edges" in data_dict or self.batch is not None
+        self.match = prepared if prepared is not None else None if self.batch is not None else \
+            model.prepare_matching(data_dict, dev) if self.have_matching else None
+        if self.batch is None:
+            self.pivot = torch.arange(self.n_nodes, dtype=torch.int32, device=dev)
+        else:
+            self.pivot = self.batch.pivot[self.batch_index, :self.n_nodes]
+            self.pivot.copy_(torch.arange(self.n_nodes, dtype=torch.int32, device=dev))
         self.edge_indices = model._edge_pairs(P, dev)[None]          # == triu(ones, 1).nonzero(): row-major upper triangle
         self.edge_valids = model._edge_mask(self.num_parts, P)
         self.traj, self.step_no, self.verifier_calls, self.n_merges = [], 0, 0, 0
         self.merged_edges: List = []
         self.data = dict(data_dict)
-        if self.have_matching:
+        if self.batch is not None:
+            view = self.batch.points(self.batch_index)
+            if tuple(data_dict["part_pcs_by_area"].shape) != (1,) + tuple(view.shape):
+                raise ValueError(f"matching_batch: part_pcs_by_area {tuple(data_dict['part_pcs_by_area'].shape)}, the matcher's batch holds "
+                                 f"{view.shape[0]} points for this puzzle")
+            view.copy_(data_dict["part_pcs_by_area"][0])
+            self.data["part_pcs_by_area"] = view[None]
+        elif self.have_matching:
             self.data["part_pcs_by_area"] = data_dict["part_pcs_by_area"].clone()      # mutated by the merges (:259-262)
         self.done = False
 
@@ -433,6 +485,8 @@ class _PuzzleState:
         """[1, 190, 7] verifier input of this puzzle from its current poses (auto_aggl.py:153-201)"""
         m, dev, P = self.m, self.dev, self.P
         x, match, pivot = self.x, self.match, self.pivot
+        if self.batch is not None:
+            raise RuntimeError("a puzzle with matching_batch gets its edge features from AutoAgglomerative._edge_features")
         # ---- edge features (:156-201) ---------------------------------------------------------
         pts_t = ops.pose_apply_points(self.data["part_pcs_by_area"][0].float().contiguous(),
                                       pivot[match["point_part"].long()].contiguous(), x[0].contiguous(), normalise=False)
