@@ -647,6 +647,25 @@ int pfpp_fragment_prepare(const float* part_pcs_gt, const int32_t* num_parts, co
                           float* part_scale, float* init_pose_t, int64_t B, int64_t P, int64_t N,
                           void* workspace, pfpp_stream_t stream);
 
+/* ---- the test split's initial frames for a group of puzzles (denoiser/dataset/dataset.py:86-109 behind :165-215) ----
+ * pfpp_test_frames = pfpp_fragment_prepare (the same two kernels: part_pcs, part_trans, part_scale and init_pose_t are bit for
+ * bit what it writes for the same inputs) and then the by-area points of the assembled shapes taken into every piece's
+ * initial frame (_anchor_coords, _move_to_init_pose). by_area float32 [M, 3] = gt_pc_by_area of the B puzzles concatenated,
+ * pt_off int64 [B+1] (pt_off[B] = M), n_pcs int32 [B, P] = by-area points per piece slot, by_area_out float32 [M, 3].
+ * For point x of piece p of puzzle b, in float64:
+ *     a = R(q_global[b])^T x - c_ref[b];   c = a - (double)(float) t[b, p];   y = R(q_part[b, p])^T c, stored as float32
+ * with c_ref (= init_pose_t) and t (= part_trans; rounded to float32 first, as the host subtracts the float32 cur_trans) from
+ * the fp64 centroid workspace through the device function frag_prepare_kernel uses, and both quaternions normalised as
+ * there.  A point's piece is the first p with i < n_pcs[b, 0] + .. + n_pcs[b, p].  A point past sum n_pcs[b], in a slot
+ * p >= num_parts[b], or of a puzzle whose ref_idx is no slot is written as zeros and not read; offsets are clamped to [0, M]
+ * (memory safety only: pfpp_hip.augment.test_frames_batch refuses such input).  No atomics: a puzzle's result depends neither
+ * on the grid nor on the other puzzles of the call.  workspace: pfpp_fragment_prepare_workspace(B, P) bytes.
+ * PFPP_EUNSUPPORTED before any launch for N > 2048, B > 65535, P > 32 or M >= 2^31; B = 0 does nothing.                  */
+int pfpp_test_frames(const float* part_pcs_gt, const int32_t* num_parts, const int32_t* ref_idx, const float* q_global,
+                     const float* q_part, float* part_pcs, float* part_trans, float* part_scale, float* init_pose_t,
+                     const float* by_area, const int64_t* pt_off, const int32_t* n_pcs, float* by_area_out, int64_t B,
+                     int64_t P, int64_t N, int64_t M, void* workspace, pfpp_stream_t stream);
+
 /* ---- 8f-2: merge step of auto_aggl (utils/node_merge_utils.py:159-222) -------------------------------------
  * pfpp_estimate_normals: pytorch3d.ops.estimate_pointcloud_normals(neighborhood_size=K) per part:
  * pts [P, N, 3] -> normals [P, N, 3] (K nearest neighbours incl. the point, covariance about the

@@ -257,6 +257,7 @@ SIGNATURES = {
     "pfpp_edge_histogram": [_p, _p, _p, _p, _p, _i64, _i64, _p],
     "pfpp_edge_features_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p],
     "pfpp_fragment_prepare": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p],
+    "pfpp_test_frames": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p],
     "pfpp_estimate_normals": [_p, _p, _i64, _i64, _i64, _p],
     "pfpp_merge_keep_mask": [_p, _p, _p, _i64, _i64, _f32, _p],
     "pfpp_fps_start": [_p, _p, _p, _i64, _i64, _i64, _p, _p],

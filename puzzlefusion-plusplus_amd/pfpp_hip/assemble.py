@@ -3,13 +3,15 @@
 
     python -m pfpp_hip.assemble (--points DIR | --features DIR) --matcher CKPT --out DIR [--denoiser CKPT] [--verifier CKPT]
                                 [--config-dir DIR [--config-name auto_aggl]] [--pc-data DIR] [--in-flight 32] [--seed 0]
-                                [--gemm f32|f16x3] [key=value ...]
+                                [--gemm f32|f16x3] [--frames host|device] [key=value ...]
 
 Per group of --in-flight puzzles (also the matcher's batch size): pfpp_hip.generate_matching_data.head_batches with the device
 assignment (one column per row) -> pfpp_hip.matching_edges.match_edges_batch -> DeviceMatches.batch_prepared() -> the join with
 pc_data and the initial frames by GeometryLatentDataset(matching=mapping) -> AutoAgglomerative.test_batch, where every puzzle
 carries data_dict["matching_batch"] and the verifier input of all puzzles in flight comes from one launch per outer iteration.  The
-matches never leave the GPU.
+matches never leave the GPU.  With --frames device the initial frames of a group (the dataset's random rotations, recentring and the
+by-area points in every piece's frame) come from one pfpp_hip.augment.test_frames_batch call instead of the dataset's per-puzzle
+scipy / numpy pass; the rotations are then drawn by torch's device generator, so a seed fixes the run but not to --frames host's.
 
 --points / --features: the matcher's input files, as generate_matching_data reads them.  The pc_data directory is the config's
 (denoiser.data.data_val_dir, as test.py's build_test_dataloader takes it) or --pc-data; a puzzle without a pc_data file is skipped
@@ -29,6 +31,7 @@ from types import SimpleNamespace as NS
 from typing import Dict, Iterator, List, Optional
 
 RESULT_KEYS = ("part_acc", "shape_cd", "rmse_r", "rmse_t")
+FRAMES = ("host", "device")              # who makes a group's initial frames: the dataset per puzzle, or pfpp_test_frames per group
 
 
 def load_loop_weights(model, denoiser_ckpt: str, verifier_ckpt: str) -> None:
@@ -62,11 +65,14 @@ class Assembler:
     in eval mode with its weights loaded; cfg its config tree (cfg.denoiser.data names max_num_part and the pc_data directory)."""
 
     def __init__(self, cfg, model, matcher: str, *, points: Optional[str] = None, features: Optional[str] = None,
-                 pc_data: Optional[str] = None, in_flight: int = 32, seed: int = 0, gemm: str = "f32"):
+                 pc_data: Optional[str] = None, in_flight: int = 32, seed: int = 0, gemm: str = "f32", frames: str = "host"):
         if (points is None) == (features is None):
             raise ValueError("Assembler: exactly one of points= and features=")
         if in_flight < 1:
             raise ValueError("Assembler: in_flight must be at least 1")
+        if frames not in FRAMES:
+            raise ValueError(f"Assembler: frames={frames!r}, one of {FRAMES}")
+        self.frames = frames
         self.cfg, self.model, self.matcher = cfg, model, matcher
         self.source, self.points = (points, True) if points is not None else (features, False)
         self.pc_data = pc_data if pc_data is not None else cfg.denoiser.data.data_val_dir
@@ -105,6 +111,16 @@ class Assembler:
                               "n_critical_pcs": nc_host[b], "matching_batch": (bo, b)}
             yield group, mapping
 
+    # ------------------------------------------------------------------------------------------------ the initial frames
+    def group_dicts(self, ds, rows, dev) -> List[dict]:
+        """the batch-of-one dicts of a group (dataset rows `rows`, their mapping entries joined): per puzzle by the dataset's host
+        arithmetic, or for the whole group by one pfpp_test_frames call (the dataset then returns the stored geometry only)"""
+        if self.frames == "device":
+            from .augment import test_frames_batch
+
+            return test_frames_batch([ds[k] for k in rows], dev)
+        return [as_batch_of_one(ds[k], dev) for k in rows]
+
     # ------------------------------------------------------------------------------------------------ the whole route
     def run(self, out_dir: Optional[str] = None, ids=None, log=print) -> List[dict]:
         """all puzzles of the source directory (or `ids`) -> one record per assembled puzzle, in the matcher's order; with out_dir,
@@ -119,11 +135,12 @@ class Assembler:
         if ids is None:
             ids, _ = list_puzzles(self.source, os.devnull)          # nothing counts as done: no <data_id>.npz is ever written
         np.random.seed(self.seed)                        # the dataset's scipy rotations draw from numpy's global generator
-        torch.manual_seed(self.seed)
+        torch.manual_seed(self.seed)                     # also the device generator frames="device" draws its rotations from
         dev = next(self.model.parameters()).device
         # pc_data is read ONCE (a dataset per group would read the whole directory per group); the group's mapping entries are
         # joined to its samples below, which is what the dataset's matching= keyword does at construction
-        ds = GeometryLatentDataset(self.cfg.denoiser, self.pc_data, -1, "test", matching={d: {} for d in ids})
+        ds = GeometryLatentDataset(self.cfg.denoiser, self.pc_data, -1, "test", device_augment=self.frames == "device",
+                                   matching={d: {} for d in ids})
         index = {s["data_id"]: k for k, s in enumerate(ds.data_list)}
         records: List[dict] = []
         fh = None
@@ -138,11 +155,9 @@ class Assembler:
                 todo = [d for d in group if d in index]
                 if not todo:
                     continue
-                dicts = []
                 for d in todo:
                     ds.data_list[index[d]].update(mapping[d])
-                    dicts.append(as_batch_of_one(ds[index[d]], dev))
-                results = self.model.test_batch(dicts)
+                results = self.model.test_batch(self.group_dicts(ds, [index[d] for d in todo], dev))
                 for d, r in zip(todo, results):
                     rec = {"data_id": int(d), **{k: float(r["metrics"][k][0]) for k in RESULT_KEYS},
                            "verifier_calls": int(r["verifier_calls"]), "merges": int(r["merges"]), "steps": int(r["steps"])}
@@ -190,7 +205,7 @@ def build_config(config_dir: Optional[str], config_name: str, overrides: List[st
     return cfg
 
 
-def main(argv: Optional[List[str]] = None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m pfpp_hip.assemble", description=__doc__.split("\n\n")[0])
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--points", help="directory of <data_id>.npz point-cloud files (the descriptor network runs in front of the head)")
@@ -205,7 +220,14 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--in-flight", type=int, default=32, help="puzzles per group: the matcher's batch size and the loop's")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gemm", choices=("f32", "f16x3"), default="f32", help="the matcher's GEMM mode")
+    ap.add_argument("--frames", choices=FRAMES, default="host",
+                    help="the initial frames of a group: by the dataset per puzzle on the host, or in one launch on the GPU")
     ap.add_argument("overrides", nargs="*", help="key=value overrides of the config tree")
+    return ap
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.in_flight < 1:
         ap.error("--in-flight must be at least 1")
@@ -243,7 +265,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     load_loop_weights(model, ckpts["denoiser"], ckpts["verifier"])
     model = model.cuda().eval()
     asm = Assembler(cfg, model, args.matcher, points=args.points, features=args.features, in_flight=args.in_flight, seed=args.seed,
-                    gemm=args.gemm)
+                    gemm=args.gemm, frames=args.frames)
     t0 = time.perf_counter()
     records = asm.run(args.out, log=lambda s: print(s, flush=True))
     dt = time.perf_counter() - t0

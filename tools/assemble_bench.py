@@ -1,4 +1,4 @@
-"""Measure matcher -> assembly loop over synthetic puzzles on one GPU, two routes alternating in one process; print one JSON line.
+"""Measure matcher -> assembly loop over synthetic puzzles on one GPU, three routes alternating in one process; print one JSON line.
 
     python tools/assemble_bench.py [--puzzles 64] [--in-flight 32] [--reps 5] [--warmup 2] [--out FILE]
 
@@ -9,12 +9,16 @@ auto_aggl line does (20 DDPM steps per outer iteration, up to 6 iterations), `--
 
 * route "files": python -m pfpp_hip.generate_matching_data --assignment device --edges device into a fresh directory, then
   GeometryLatentDataset from that directory and AutoAgglomerative.test_batch per group (prepare_matching and edge_features per puzzle);
-* route "assembler": pfpp_hip.assemble.Assembler (matches stay on the device, one edge-feature launch per outer iteration).
+* route "assembler": pfpp_hip.assemble.Assembler (matches stay on the device, one edge-feature launch per outer iteration);
+* route "assembler_device_frames": the same with frames="device" (a group's initial frames from one pfpp_test_frames call instead of
+  the dataset's per-puzzle host arithmetic).  Its rotations come from the device generator, so its loop sees other inputs than the
+  two routes above: its records are not compared with theirs.
 
-Both routes get the same seeds.  Wall clock per route run, ending in a device synchronise; `--warmup` pairs, then `--reps` pairs,
+All routes get the same seeds.  Wall clock per route run, ending in a device synchronise; `--warmup` pairs, then `--reps` pairs,
 medians with all values listed.  The edge-feature stage of every outer iteration is bracketed by HIP events, and the calls of the HIP
 entries inside it are counted.  On a commit without pfpp_hip.assemble only the "files" route runs (the baseline), with the events
-around every per-puzzle edge_features() call."""
+around every per-puzzle edge_features() call.  The frame preparation of a group (Assembler.group_dicts: dataset items to the
+batch-of-one dicts on the device) is bracketed by the host clock, ending in a device synchronise, for both Assembler routes."""
 from __future__ import annotations
 
 import argparse
@@ -181,16 +185,34 @@ def main() -> int:
             shutil.rmtree(mdir)
             return [(float(r["metrics"]["part_acc"][0]), r["steps"], r["verifier_calls"], r["merges"]) for r in res]
 
-        def assembler_route(rep: int):
-            asm = assemble.Assembler(cfg, model, str(root / "jigsaw.ckpt"), features=str(root / "features"), in_flight=args.in_flight, seed=0)
+        frame_s = []                                        # wall clock of every group_dicts call of the route that is running
+        with_frames = assemble is not None and hasattr(assemble.Assembler, "group_dicts")
+        if with_frames:
+            plain_group_dicts = assemble.Assembler.group_dicts
+
+            def timed_group_dicts(self, ds, rows, dev_):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = plain_group_dicts(self, ds, rows, dev_)
+                torch.cuda.synchronize()
+                frame_s.append(time.perf_counter() - t0)
+                return out
+
+            assemble.Assembler.group_dicts = timed_group_dicts
+
+        def assembler_route(rep: int, **kw):
+            asm = assemble.Assembler(cfg, model, str(root / "jigsaw.ckpt"), features=str(root / "features"), in_flight=args.in_flight, seed=0, **kw)
             recs = asm.run(None, ids=ids, log=lambda s: None)
             return [(r["part_acc"], r["steps"], r["verifier_calls"], r["merges"]) for r in recs]
 
         routes = {"files": files_route}
         if assemble is not None:
             routes["assembler"] = assembler_route
+        if with_frames:
+            routes["assembler_device_frames"] = lambda rep: assembler_route(rep, frames="device")
         walls = {k: [] for k in routes}
         stage_ms = {k: [] for k in routes}
+        frames_ms = {k: [] for k in routes}                 # per timed run: the sum over its groups
         launches, last = {}, {}
         import io
         from contextlib import redirect_stdout
@@ -204,8 +226,11 @@ def main() -> int:
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 ms, counted = timer.take()
+                spent, frame_s[:] = list(frame_s), []
                 if rep >= args.warmup:
                     walls[name].append(dt)
+                    if spent:
+                        frames_ms[name].append(1e3 * sum(spent))
                     stage_ms[name] += ms
                     launches[name] = counted
         line = {"bench": "assemble", "puzzles": len(ids), "in_flight": args.in_flight, "reps": args.reps, "warmup_pairs": args.warmup,
@@ -219,6 +244,11 @@ def main() -> int:
                           "edge_stage_ms_median": round(statistics.median(stage_ms[name]), 4) if stage_ms[name] else None,
                           "edge_stage_ms_min_max": [round(min(stage_ms[name]), 4), round(max(stage_ms[name]), 4)] if stage_ms[name] else None,
                           "edge_stage_events": len(stage_ms[name])}
+            if frames_ms[name]:
+                f = frames_ms[name]
+                line[name]["frames_ms_per_run_median"] = round(statistics.median(f), 3)
+                line[name]["frames_ms_per_run_all"] = [round(x, 3) for x in f]
+                line[name]["frames_measure"] = "host clock around every group's frame preparation, device synchronise before and after, summed over the groups of a run"
             if launches.get(name):
                 full = [c for c in launches[name] if c["puzzles"] == max(x["puzzles"] for x in launches[name])]
                 line[name]["hip_entry_calls_per_stage"] = full[0]
