@@ -321,14 +321,28 @@ int pfpp_gemm_planes(const pfpp_gemm_planes_args* args, pfpp_stream_t stream);
  * gb += colsum(dY) / dy.scale; gb may be NULL).  Every output tile runs the whole contraction in one accumulator chain (no K split,
  * no workspace, no reduction launch; deterministic); the problems' tiles are dealt to the XCDs as one concatenated list.
  * variant: 0 = the library's choice (= 2: 256 x 128 tiles, 160 workgroups for a block's six problems); alternatives:
- * 3 = 128 x 128 tiles, 6 / 7 = 128 x 64 (three / two stages).       */
+ * 3 = 128 x 128 tiles, 6 / 7 = 128 x 64 (three / two stages).
+ * A job with an update block (upd != NULL) does not touch gw at all: a tile that has walked the whole contraction holds the FINAL
+ * gradient of its weights, g = acc * (1 / (dy.scale * x.scale)) — bit for bit what the plain job stores into a ZEROED gw — and applies
+ * pfpp_adamw_guarded's update (zero_grad: there is nothing to clear) to the matching elements of p, m, v, hi, lo [M, N] in its
+ * epilogue: same element function (csrc/adamw_element.h), same non-finite test (the element keeps p, m, v and its planes, the flag is
+ * raised and the count grows by one).  Valid where the gradient has this one producer and the update is its one consumer, which
+ * would zero it: the caller's invariant (pfpp_tlayers_bwd: opt_fused_dw).  gb is accumulated as ever.  The hyper-parameters and the
+ * flag belong to the launch: every update block of a call must carry the same ones.  */
 #define PFPP_DW_GROUP_MAX 8
+typedef struct pfpp_dw_update {
+  float *p, *m, *v;    /* [M, N] fp32: parameter, first and second moment */
+  void *hi, *lo;       /* [M, N] split-f16 planes of p (both or neither) */
+  float lr, beta1, beta2, eps, weight_decay, bc1, bc2, g_scale;      /* as pfpp_adamw_guarded takes them */
+  int32_t* overflow;   /* int32[2] or NULL (no guard) */
+} pfpp_dw_update;
 typedef struct pfpp_dw_job {
   pfpp_planes dy;      /* [K, M] */
   pfpp_planes x;       /* [K, N] */
-  float* gw;           /* [M, N] fp32, accumulated in place */
+  float* gw;           /* [M, N] fp32, accumulated in place (with upd: neither read nor written; may be NULL) */
   float* gb;           /* [M] fp32 or NULL */
   int64_t M, N;
+  const pfpp_dw_update* upd;   /* NULL: accumulate into gw */
 } pfpp_dw_job;
 int pfpp_gemm_dw_group(const pfpp_dw_job* jobs, int32_t n_jobs, int64_t K, int32_t variant, pfpp_stream_t stream);
 /* name of the kernel instantiation the calling thread's last pfpp_gemm, pfpp_gemm_planes, pfpp_gemm_dw_group, pfpp_gemm_grad or
@@ -896,14 +910,21 @@ int pfpp_adamw_zero(float* p, float* g, float* m, float* v, void* hi, void* lo, 
 int pfpp_adamw_guarded(float* p, float* g, float* m, float* v, void* hi, void* lo, int64_t n,
                        float lr, float beta1, float beta2, float eps, float weight_decay, float bc1,
                        float bc2, float g_scale, int zero_grad, int32_t* overflow, pfpp_stream_t stream);
+/* pfpp_adamw_guarded over n_ranges ranges [off[k], off[k] + len[k]) of the same buffers in ONE launch (off, len: HOST arrays of element
+ * offsets / counts, at most PFPP_ADAMW_RANGES_MAX; empty ranges are skipped): the biases, LayerNorm affine and padding of a transformer
+ * layer's slice, whose matrices pfpp_gemm_dw_group updates in its epilogue (pfpp_dw_update).  Element for element what
+ * pfpp_adamw_guarded(p + off[k], ..., len[k], ...) gives, overflow flag and count included. */
+#define PFPP_ADAMW_RANGES_MAX 16
+int pfpp_adamw_ranges(float* p, float* g, float* m, float* v, void* hi, void* lo, const int64_t* off, const int64_t* len, int32_t n_ranges,
+                      float lr, float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2, float g_scale,
+                      int zero_grad, int32_t* overflow, pfpp_stream_t stream);
 /* Adam over a list of tensors in a handful of launches (Jigsaw_matching/model/modules/matching_base_model.py:499-515: one
  * torch.optim.Adam / AdamW over self.parameters(), which torch steps tensor by tensor or through its own multi-tensor path).  p, g, m,
  * v: HOST arrays of n_tensors device pointers, n: host array of element counts (>= 0; a tensor with n == 0 is skipped and may have null
  * pointers), bc1 / bc2: host arrays of the tensors' own bias corrections 1 - beta^step (torch keeps `step` per parameter; a parameter
  * without a gradient in earlier steps has a smaller one).  Per element the update is pfpp_adamw's, bit for bit (no planes, no
- * zero_grad, no guard): the kernel does not repeat adamw_kernel's source expressions, whose contraction the compiler chooses per
- * kernel, but writes out the fused multiply-adds adamw_kernel<false> compiles to on gfx950 under contract(off); the GPU test that
- * compares the two bitwise is the guard should a compiler fuse adamw_kernel differently.  g is not written.  The descriptors travel
+ * zero_grad, no guard): both kernels call the one element function of csrc/adamw_element.h, whose fused multiply-adds are written
+ * out under contract(off).  g is not written.  The descriptors travel
  * in the kernel-argument struct
  * (<= 4 KB, no device-side table): a launch holds at most PFPP_ADAM_MULTI_MAX_TENSORS tensors and PFPP_ADAM_MULTI_MAX_BLOCKS
  * workgroups of PFPP_ADAM_MULTI_CHUNK elements; tensors are taken in order, and one that the block capacity cuts goes on in the next
@@ -1024,6 +1045,11 @@ typedef struct pfpp_tlayers_args {
   float* ada_gw; float* ada_gb;                 /* [2 n_layers, 2C, C], [2 n_layers, 2C] gradients, accumulated */
   const pfpp_tlayer_adamw* ada_adamw_w;         /* [n_layers] or NULL */
   const pfpp_tlayer_adamw* ada_adamw_b;         /* [n_layers] or NULL */
+  /* backward, != 0: the caller vouches that the matrices' ranges of the gradient buffers are ZERO on entry.  Where the layer's update
+   * is also armed with opt_zero_grad on a side stream and the grouped weight-gradient launch is on, a block's six matrices are then
+   * updated in that launch's epilogue (pfpp_dw_update) and never pass through memory — their gradient ranges stay zero — and the rest
+   * of the layer's slice takes one pfpp_adamw_ranges launch where pfpp_adamw_guarded ran.  Same p, m, v, planes and flag, bit for bit. */
+  int32_t opt_fused_dw;
 } pfpp_tlayers_args;
 int64_t pfpp_tlayers_frag_bytes(int64_t C, int64_t inner);
 int64_t pfpp_tlayers_fwd_bytes(int64_t M, int64_t C, int64_t H, int64_t inner);

@@ -32,6 +32,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "adamw_element.h"
 #include "gemm_common.h"
 #include "lds_asm.h"
 
@@ -209,11 +210,102 @@ __device__ __forceinline__ void epilogue_wide(const GemmP& p, f32x16 (&acc)[MT][
   }
 }
 
+// The update epilogue of the grouped weight-gradient launch (pfpp_dw_update): the tile holds the final gradient of its weights, so
+// instead of adding it into the gradient buffer for an AdamW launch to read back and zero, it applies that update here.  Same walk as
+// epilogue_wide (LDS patch, 16-byte rows), and the gradient is formed by the same operations in the same order: acc * alpha, + the
+// absent bias (0.0f), + the residual, which for a gradient accumulated onto a zeroed buffer is 0.0f — so g has the bits the plain job
+// stores, the sign of a zero included ((-0) + 0 = +0 both times).  Then adamw_kernel's steps: g * g_scale, the non-finite test, the
+// element function, the split of the new parameter.  gw is neither read nor written.
+struct DwUpd {
+  float *p, *m, *v;
+  _Float16 *hi, *lo;
+};
+
+template <int MT, int NT>
+__device__ __forceinline__ void epilogue_adamw(const GemmP& p, const DwUpd& u, const pfpp_adamw_hp& hp, int* overflow, f32x16 (&acc)[MT][NT],
+                                               int row_w, int col_w, int lane, uint32_t patch) {
+  const int l31 = lane & 31, lhi = lane >> 5;
+  const float alpha = p.alpha;
+  constexpr int ROWB = NT * 128;
+  constexpr int LPR = 8 * NT;
+  constexpr int RPI = 64 / LPR;
+  const int rcol = (lane % LPR) * 4, rrow = lane / LPR;
+  typedef _Float16 half4v __attribute__((ext_vector_type(4)));
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const f32x16 t = acc[i][j];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int r = (e & 3) + 8 * (e >> 2) + 4 * lhi;
+        asm volatile("ds_write_b32 %0, %1" ::"v"(patch + r * ROWB + (j * 32 + l31) * 4), "v"(t[e]) : "memory");
+      }
+    }
+    f32x4 vv[32 / RPI];
+#pragma unroll
+    for (int k = 0; k < 32 / RPI; ++k)
+      asm volatile("ds_read_b128 %0, %1" : "=v"(vv[k]) : "v"(patch + (rrow + k * RPI) * ROWB + rcol * 4) : "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < 32 / RPI; k += 4)
+      asm volatile("" : "+v"(vv[k]), "+v"(vv[k + 1]), "+v"(vv[k + 2]), "+v"(vv[k + 3]));
+#pragma unroll
+    for (int k = 0; k < 32 / RPI; ++k) {
+      const int row = row_w + i * 32 + rrow + k * RPI;
+      const int col = col_w + rcol;
+      if (row >= p.M || col >= p.N) continue;
+      const int64_t idx = (int64_t)row * p.N + col;
+      const float4 p4 = *reinterpret_cast<const float4*>(u.p + idx);
+      const float4 m4 = *reinterpret_cast<const float4*>(u.m + idx);
+      const float4 v4 = *reinterpret_cast<const float4*>(u.v + idx);
+      float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, sq[4] = {v4.x, v4.y, v4.z, v4.w};
+      bool bad[4];
+      int n_bad = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float g = (vv[k][c] * alpha + 0.0f) + 0.0f;      // epilogue_wide without bias onto a zeroed residual
+        const float gr = g * hp.g_scale;
+        bad[c] = overflow != nullptr && pfpp_adamw_nonfinite(gr);
+        n_bad += bad[c] ? 1 : 0;
+        float m1 = mm[c], v1 = sq[c];
+        const float p1 = pfpp_adamw_element(pp[c], gr, m1, v1, hp.decay, hp.w1, hp.beta2, hp.w2, hp.eps, hp.step_size, hp.inv_sqrt_bc2);
+        if (!bad[c]) { pp[c] = p1; mm[c] = m1; sq[c] = v1; }
+      }
+      half4v hi, lo;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) PFPP_SPLIT_TO(pp[c], hi[c], lo[c]);
+      // (a skipped element's p, m, v go back as they were read)
+      *reinterpret_cast<float4*>(u.p + idx) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+      *reinterpret_cast<float4*>(u.m + idx) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+      *reinterpret_cast<float4*>(u.v + idx) = make_float4(sq[0], sq[1], sq[2], sq[3]);
+      if (u.hi) {
+        if (n_bad == 0) {
+          *reinterpret_cast<half4v*>(u.hi + idx) = hi;
+          *reinterpret_cast<half4v*>(u.lo + idx) = lo;
+        } else {                                     // the planes of a skipped element are left as they are, whatever they hold
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (!bad[c]) { u.hi[idx + c] = hi[c]; u.lo[idx + c] = lo[c]; }
+        }
+      }
+      if (n_bad != 0) {
+        atomicOr(overflow, 1);
+        atomicAdd(overflow + 1, n_bad);
+      }
+    }
+  }
+}
+
 // One workgroup = one output tile.  NS-stage DMA ring; see the header for the schedule.
 // EXT: the (tile, K chunk) of this workgroup comes from the caller (ext_tile of the problem's row-major tile list, whole contraction)
 // instead of blockIdx — the grouped weight-gradient launch, where a workgroup first finds its problem in a table.
-template <int MT, int NT, int WM, int WN, int NS, bool AK, bool WK, bool AF = false, bool X1 = false, bool CS = false, bool EXT = false>
-__device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
+// UPD (with EXT): a tile of a problem that carries an update block (upd->p != null) ends in epilogue_adamw instead of a store.
+template <int MT, int NT, int WM, int WN, int NS, bool AK, bool WK, bool AF = false, bool X1 = false, bool CS = false, bool EXT = false,
+          bool UPD = false>
+__device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0, const DwUpd* upd = nullptr, const pfpp_adamw_hp* hp = nullptr,
+                                        int* overflow = nullptr) {
+  static_assert(!UPD || EXT, "the update epilogue belongs to the grouped weight-gradient launch");
   static_assert(!(AF && AK), "an fp32 A operand is row-major");
   static_assert(!CS || (AK && !X1), "column sums ride with a k-major split A operand (dW = dY^T . X)");
   static_assert(!(AF && X1), "the single-pass mode takes pre-split operands");
@@ -651,6 +743,13 @@ __device__ __forceinline__ void pl_body(const GemmP& p, int ext_tile = 0) {
       }
     }
   }
+  if constexpr (UPD) {
+    if (upd->p) {
+      __builtin_amdgcn_s_barrier();      // every wave is done with the DMA ring: its first bytes become the transposition patches
+      epilogue_adamw<MT, NT>(p, *upd, *hp, overflow, acc, m0 + wm * 32 * MT, n0 + wn * 32 * NT, lane, lds0 + wave * (32 * NT * 128));
+      return;
+    }
+  }
   if (p.split_ws && p.split_k > 1) {
     // K split with a workspace: this chunk's alpha * acc goes to its own dense [M, N] slab with 16-byte stores; pl_reduce_kernel
     // adds the slabs in chunk order afterwards (deterministic; fp32 atomics on a shared C measured 1.2 TB/s: every chunk of a
@@ -781,6 +880,14 @@ struct DwGroupP {
   int first_tile[PFPP_DW_GROUP_MAX];
   int n;
 };
+// the update blocks of a launch that has any (a second kernel argument: the plain launch's argument segment stays as it was).
+// u[j].p == null: problem j accumulates into its gradient buffer as in the plain launch
+struct DwGroupU {
+  DwUpd u[PFPP_DW_GROUP_MAX];
+  pfpp_adamw_hp hp;
+  int* overflow;
+};
+static_assert(sizeof(DwGroupP) + sizeof(DwGroupU) <= 4096, "the kernel-argument segment of pfpp_gemm_dw_group is kept within 4 KB");
 
 template <int MT, int NT, int WM, int WN, int NS>
 __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_pl_dwgroup_kernel(const DwGroupP g) {
@@ -792,17 +899,37 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_pl_dwgroup_kernel(const 
   pl_body<MT, NT, WM, WN, NS, true, true, false, false, true, true>(g.p[j], t - g.first_tile[j]);
 }
 
+// (an overload of the same family name with a sixth template argument: profilers and bench.py's roofline table know the family)
+template <int MT, int NT, int WM, int WN, int NS, bool UPD>
+__global__ __launch_bounds__(64 * WM * WN, 2) void gemm_pl_dwgroup_kernel(const DwGroupP g, const DwGroupU gu) {
+  static_assert(UPD, "the plain launch is the five-argument template");
+  const int t = remap_tile(blockIdx.x, gridDim.x);
+  int j = 0;
+#pragma unroll
+  for (int k = 1; k < PFPP_DW_GROUP_MAX; ++k)
+    if (k < g.n && t >= g.first_tile[k]) j = k;
+  pl_body<MT, NT, WM, WN, NS, true, true, false, false, true, true, true>(g.p[j], t - g.first_tile[j], &gu.u[j], &gu.hp, gu.overflow);
+}
+
 template <int MT, int NT, int WM, int WN, int NS>
-int launch_dwgroup(DwGroupP& g, const pfpp_dw_job* jobs, hipStream_t st) {
+int launch_dwgroup(DwGroupP& g, const DwGroupU* gu, const pfpp_dw_job* jobs, hipStream_t st) {
   using C = Cfg<MT, NT, WM, WN, NS, false>;
-  constexpr auto kern = gemm_pl_dwgroup_kernel<MT, NT, WM, WN, NS>;
-  (void)pfpp_allow_dyn_lds<kern>();
   int tiles = 0;
   for (int j = 0; j < g.n; ++j) {
     g.p[j].tiles_n = (int)((jobs[j].N + C::BN - 1) / C::BN);
     g.first_tile[j] = tiles;
     tiles += (int)((jobs[j].M + C::BM - 1) / C::BM) * g.p[j].tiles_n;
   }
+  if (gu) {
+    constexpr void (*kern)(const DwGroupP, const DwGroupU) = gemm_pl_dwgroup_kernel<MT, NT, WM, WN, NS, true>;
+    (void)pfpp_allow_dyn_lds<kern>();
+    static const KernelName name("gemm_pl_dwgroup_kernel<%d, %d, %d, %d, %d, true>", MT, NT, WM, WN, NS);
+    report_kernel(name);
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(C::NTHR), C::SMEM, st, g, *gu);
+    return pfpp::check_launch("pfpp_gemm_dw_group");
+  }
+  constexpr void (*kern)(const DwGroupP) = gemm_pl_dwgroup_kernel<MT, NT, WM, WN, NS>;
+  (void)pfpp_allow_dyn_lds<kern>();
   static const KernelName name("gemm_pl_dwgroup_kernel<%d, %d, %d, %d, %d>", MT, NT, WM, WN, NS);
   report_kernel(name);
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(C::NTHR), C::SMEM, st, g);
@@ -1020,21 +1147,44 @@ extern "C" int pfpp_gemm_dw_group(const pfpp_dw_job* jobs, int32_t n_jobs, int64
   pl::DwGroupP g;
   memset(&g, 0, sizeof(g));
   g.n = n_jobs;
+  pl::DwGroupU gu;
+  memset(&gu, 0, sizeof(gu));
+  const pfpp_dw_update* first_upd = nullptr;
   for (int j = 0; j < n_jobs; ++j) {
     const pfpp_dw_job& q = jobs[j];
-    PFPP_REQUIRE(q.dy.hi && q.dy.lo && q.x.hi && q.x.lo && q.gw, "null pointer");
+    PFPP_REQUIRE(q.dy.hi && q.dy.lo && q.x.hi && q.x.lo && (q.gw || q.upd), "null pointer");
+    if (const pfpp_dw_update* u = q.upd) {
+      PFPP_REQUIRE(u->p && u->m && u->v && !u->hi == !u->lo, "update block: null pointer (hi and lo go together)");
+      PFPP_REQUIRE(pfpp::aligned16(u->p) && pfpp::aligned16(u->m) && pfpp::aligned16(u->v) && pfpp::aligned16(u->hi) && pfpp::aligned16(u->lo),
+                   "update block: 16-byte aligned p, m, v and planes");
+      PFPP_REQUIRE(u->bc1 > 0.0f && u->bc2 > 0.0f, "bias corrections must be positive");
+      if (!first_upd) first_upd = u;
+      PFPP_REQUIRE(u->lr == first_upd->lr && u->beta1 == first_upd->beta1 && u->beta2 == first_upd->beta2 && u->eps == first_upd->eps &&
+                   u->weight_decay == first_upd->weight_decay && u->bc1 == first_upd->bc1 && u->bc2 == first_upd->bc2 &&
+                   u->g_scale == first_upd->g_scale && u->overflow == first_upd->overflow,
+                   "the update blocks of one launch share their hyper-parameters and flag");
+      pl::DwUpd& d = gu.u[j];
+      d.p = u->p; d.m = u->m; d.v = u->v; d.hi = (_Float16*)u->hi; d.lo = (_Float16*)u->lo;
+    }
     PFPP_REQUIRE(q.M >= 8 && q.N >= 8 && q.M % 8 == 0 && q.N % 8 == 0 && q.M < (1ll << 31) && q.N < (1ll << 31), "M, N: multiples of 8");
     PFPP_REQUIRE(pfpp::aligned16(q.dy.hi) && pfpp::aligned16(q.dy.lo) && pfpp::aligned16(q.x.hi) && pfpp::aligned16(q.x.lo) &&
-                 pfpp::aligned16(q.gw), "16-byte aligned operands");
+                 (q.upd || pfpp::aligned16(q.gw)), "16-byte aligned operands");
     PFPP_REQUIRE(q.dy.scale > 0.0f && q.x.scale > 0.0f, "plane scales");
     GemmP& p = g.p[j];                       // (zeroed above: every optional pointer null, pool / act / stats off)
     p.Ahi = q.dy.hi; p.Alo = q.dy.lo; p.Whi = q.x.hi; p.Wlo = q.x.lo;
-    p.C = q.gw; p.residual = q.gw;           // C += alpha * acc: the in-place residual of the wide epilogue
+    if (!q.upd) { p.C = q.gw; p.residual = q.gw; }      // C += alpha * acc: the in-place residual of the wide epilogue (update block: no C at all)
     p.M = (int)q.M; p.N = (int)q.N; p.K = (int)((K + 31) / 32 * 32); p.k_valid = (int)K;
     p.lda = q.M; p.ldw = q.N; p.ldc = q.N; p.ldr = q.N;
     p.act = PFPP_ACT_NONE; p.zdiv = 1; p.split_k = 1; p.stats_copies = 1;
     p.alpha = 1.0f / (q.dy.scale * q.x.scale);
     p.csum = q.gb; p.csum_alpha = 1.0f / q.dy.scale;
+  }
+  const pl::DwGroupU* gup = nullptr;
+  if (first_upd) {
+    gu.hp = pfpp_adamw_hp_of(first_upd->lr, first_upd->beta1, first_upd->beta2, first_upd->eps, first_upd->weight_decay, first_upd->bc1,
+                             first_upd->bc2, first_upd->g_scale);
+    gu.overflow = first_upd->overflow;
+    gup = &gu;
   }
   hipStream_t st = pfpp::as_stream(stream);
   // default: the 256 x 128 tile (8 waves, one workgroup per CU).  Measured on a block's six problems at 3,850 tokens
@@ -1042,10 +1192,10 @@ extern "C" int pfpp_gemm_dw_group(const pfpp_dw_job* jobs, int32_t n_jobs, int64
   // launches + their slab reductions) although its 160 tiles leave 96 CUs without one; in the overlapped training iteration 6.06 ms
   // against 6.28 (small tiles) and 6.23 (separate launches) — profiles/r05a_ab_dwgroup.txt
   switch (variant ? variant : 2) {
-    case 6: return pl::launch_dwgroup<2, 1, 2, 2, 3>(g, jobs, st);       // 128 x 64, three stages (72 KB: two workgroups per CU)
-    case 7: return pl::launch_dwgroup<2, 1, 2, 2, 2>(g, jobs, st);       // 128 x 64, two stages (48 KB: three per CU)
-    case 2: return pl::launch_dwgroup<2, 2, 4, 2, 3>(g, jobs, st);       // 256 x 128, 8 waves
-    default: return pl::launch_dwgroup<2, 2, 2, 2, 2>(g, jobs, st);      // 128 x 128, two stages (64 KB: two per CU)
+    case 6: return pl::launch_dwgroup<2, 1, 2, 2, 3>(g, gup, jobs, st);       // 128 x 64, three stages (72 KB: two workgroups per CU)
+    case 7: return pl::launch_dwgroup<2, 1, 2, 2, 2>(g, gup, jobs, st);       // 128 x 64, two stages (48 KB: three per CU)
+    case 2: return pl::launch_dwgroup<2, 2, 4, 2, 3>(g, gup, jobs, st);       // 256 x 128, 8 waves
+    default: return pl::launch_dwgroup<2, 2, 2, 2, 2>(g, gup, jobs, st);      // 128 x 128, two stages (64 KB: two per CU)
   }
 }
 

@@ -316,11 +316,40 @@ extern "C" int pfpp_tlayers_bwd(const pfpp_tlayers_args* a, int32_t layer_lo, in
   // pfpp_gemm_planes launch (+ slab reduction) per weight as through round 4 (the cross-check of the tests)
   const int dw_group = getenv("PFPP_TRAIN_DW_GROUP") ? atoi(getenv("PFPP_TRAIN_DW_GROUP")) : 1;          // (read per call: the tests switch it)
   const int dw_group_variant = getenv("PFPP_TRAIN_DW_GROUP_VARIANT") ? atoi(getenv("PFPP_TRAIN_DW_GROUP_VARIANT")) : 0;
+  const int lab_skip = getenv("PFPP_LAB_SKIP_DW_LAYERS") ? atoi(getenv("PFPP_LAB_SKIP_DW_LAYERS")) : 0;      // (see below)
   pfpp_dw_job dw_jobs[PFPP_DW_GROUP_MAX];
   int dw_slots[PFPP_DW_GROUP_MAX];
   int n_dw = 0;
+  // AdamW in the grouped launch's epilogue (pfpp_dw_update).  In the armed single-rank step with zero_grad the gradient of a block
+  // matrix has one producer (a tile of the grouped launch, which walks the whole contraction) and one consumer (the layer's AdamW,
+  // which zeroes it): it need not pass through memory.  Only where all of that holds AND the caller vouches for zeroed matrix ranges
+  // (opt_fused_dw: "accumulate onto zero" is then the value itself); every other case takes the path below unchanged.  A pure function
+  // of the arguments and the switches this function already reads.
+  const bool fused_dw = a->opt_fused_dw && a->adamw && a->opt_zero_grad && side && dw_group == 1 && lab_skip == 0;
+  pfpp_dw_update dw_upd[PFPP_DW_GROUP_MAX];
+  int64_t upd_off[PFPP_ADAMW_RANGES_MAX], upd_len[PFPP_ADAMW_RANGES_MAX];      // the matrices of the current layer updated that way
+  int n_upd = 0;
   auto flush_dw = [&]() -> int {
     if (n_dw == 0) return PFPP_OK;
+    if (fused_dw) {
+      // (the order-after below puts the launch behind every main-stream kernel queued so far: all input-gradient GEMMs of the layer,
+      // the last readers of its weights, are among them - a flush happens at the layer's end only when dw_group == 1)
+      const pfpp_tlayer_adamw& ad = a->adamw[cur_layer];
+      for (int q = 0; q < n_dw; ++q) {
+        pfpp_dw_job& job = dw_jobs[q];
+        const int64_t off = job.gw - ad.g, len = job.M * job.N;
+        if (job.gw < ad.g || off + len > ad.n || n_upd == PFPP_ADAMW_RANGES_MAX - 1) continue;      // not a matrix of this slice: the plain job
+        pfpp_dw_update& u = dw_upd[q];
+        u.p = ad.p + off; u.m = ad.m + off; u.v = ad.v + off;
+        u.hi = ad.hi ? static_cast<char*>(ad.hi) + 2 * off : nullptr;
+        u.lo = ad.lo ? static_cast<char*>(ad.lo) + 2 * off : nullptr;
+        if (!(pfpp::aligned16(u.p) && pfpp::aligned16(u.m) && pfpp::aligned16(u.v) && pfpp::aligned16(u.hi) && pfpp::aligned16(u.lo))) continue;
+        u.lr = a->lr; u.beta1 = a->beta1; u.beta2 = a->beta2; u.eps = a->eps; u.weight_decay = a->weight_decay;
+        u.bc1 = a->bc1; u.bc2 = a->bc2; u.g_scale = a->opt_g_scale; u.overflow = a->overflow;
+        job.upd = &u;
+        upd_off[n_upd] = off; upd_len[n_upd] = len; ++n_upd;
+      }
+    }
     if (side) TL_CALL(order_after(side_s, main_s));
     TL_CALL(pfpp_gemm_dw_group(dw_jobs, n_dw, M, dw_group_variant, side_t));
     for (int q = 0; q < n_dw; ++q)
@@ -333,7 +362,6 @@ extern "C" int pfpp_tlayers_bwd(const pfpp_tlayers_args* a, int32_t layer_lo, in
   // WRONG gradients: no dW for the last k layers to run) applies to the grouped launch too; PFPP_DW_SPLITS only means something with
   // PFPP_TRAIN_DW_GROUP=0 (the grouped launch has no K split)
   const int dw_splits = getenv("PFPP_DW_SPLITS") ? atoi(getenv("PFPP_DW_SPLITS")) : 0;
-  const int lab_skip = getenv("PFPP_LAB_SKIP_DW_LAYERS") ? atoi(getenv("PFPP_LAB_SKIP_DW_LAYERS")) : 0;
   // INVARIANT the grouped path relies on: between two flush_dw() calls every dY slot is acquired (fresh) at most ONCE - the slots'
   // read events are recorded at flush time only, so a slot re-acquired and rewritten before the flush would race with the queued
   // read of its first tenant.  Holds today: a block uses each of its slots for one dY, and every block ends in flush_dw().
@@ -344,7 +372,7 @@ extern "C" int pfpp_tlayers_bwd(const pfpp_tlayers_args* a, int32_t layer_lo, in
         if (k >= 0 && dw_slots[q] == k) { pfpp::set_error("pfpp_tlayers_bwd: slot %d queued twice before a flush", k); return PFPP_EINVAL; }
       if (n_dw == PFPP_DW_GROUP_MAX) TL_CALL(flush_dw());
       pfpp_dw_job& q = dw_jobs[n_dw];
-      q.dy = dyp; q.x = xp; q.gw = gw; q.gb = gb; q.M = n_out; q.N = n_in;
+      q.dy = dyp; q.x = xp; q.gw = gw; q.gb = gb; q.M = n_out; q.N = n_in; q.upd = nullptr;
       dw_slots[n_dw++] = k;
       return PFPP_OK;
     }
@@ -454,8 +482,25 @@ extern "C" int pfpp_tlayers_bwd(const pfpp_tlayers_args* a, int32_t layer_lo, in
       // optimizer in the backward: the layer's slice of the flat buffer is final once its weight gradients (side stream) and its
       // LayerNorm gradients (main stream, all queued by now) have run
       const pfpp_tlayer_adamw& ad = a->adamw[i];
-      TL_CALL(pfpp_adamw_guarded(ad.p, ad.g, ad.m, ad.v, ad.hi, ad.lo, ad.n, a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, a->bc1, a->bc2,
-                                 a->opt_g_scale, a->opt_zero_grad, a->overflow, side_t));
+      if (n_upd > 0) {
+        // the matrices were updated in the grouped launch's epilogue: what lies between them in the slice (biases, the LayerNorm affine,
+        // padding) takes the ordinary update, in one launch over the gaps
+        for (int x = 1; x < n_upd; ++x)          // by offset (insertion sort of at most 15 entries)
+          for (int y = x; y > 0 && upd_off[y - 1] > upd_off[y]; --y) { std::swap(upd_off[y - 1], upd_off[y]); std::swap(upd_len[y - 1], upd_len[y]); }
+        int64_t r_off[PFPP_ADAMW_RANGES_MAX], r_len[PFPP_ADAMW_RANGES_MAX], pos = 0;
+        int n_r = 0;
+        for (int x = 0; x <= n_upd; ++x) {
+          const int64_t end = x < n_upd ? upd_off[x] : ad.n;
+          if (end > pos) { r_off[n_r] = pos; r_len[n_r] = end - pos; ++n_r; }
+          if (x < n_upd) pos = upd_off[x] + upd_len[x];
+        }
+        n_upd = 0;
+        TL_CALL(pfpp_adamw_ranges(ad.p, ad.g, ad.m, ad.v, ad.hi, ad.lo, r_off, r_len, n_r, a->lr, a->beta1, a->beta2, a->eps, a->weight_decay,
+                                  a->bc1, a->bc2, a->opt_g_scale, a->opt_zero_grad, a->overflow, side_t));
+      } else {
+        TL_CALL(pfpp_adamw_guarded(ad.p, ad.g, ad.m, ad.v, ad.hi, ad.lo, ad.n, a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, a->bc1,
+                                   a->bc2, a->opt_g_scale, a->opt_zero_grad, a->overflow, side_t));
+      }
     }
     if (a->ada_se && side) {
       // the block's two AdaLN linears (attention.py:21-25): dmods rows 2 i, 2 i + 1 are final (both LayerNorm backward launches of

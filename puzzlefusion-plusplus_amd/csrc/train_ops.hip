@@ -3,6 +3,7 @@
 // streams its operands once (float4 where the layout allows); column reductions finish with fp32
 // hardware atomics.  The contractions live in gemm_grad.hip, the attention backward in
 // attention_bwd.hip.
+#include "adamw_element.h"
 #include "pfpp_common.h"
 
 namespace {
@@ -582,7 +583,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   float gr = in ? g[i] * g_scale : 0.0f;
   if (in && zero_g) g[i] = 0.0f;                      // optimizer.zero_grad() in the same pass (no separate 230 MB memset)
   if (GUARD) {
-    const bool bad = !(fabsf(gr) <= 3.0e38f);         // inf or NaN
+    const bool bad = pfpp_adamw_nonfinite(gr);        // inf or NaN
     const unsigned long long mask = __ballot(bad);
     if (mask != 0ull && (threadIdx.x & 63) == 0) {
       atomicOr(overflow, 1);
@@ -591,12 +592,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     if (bad) return;
   }
   if (!in) return;
-  float pp = p[i] * decay;
-  float mm = m[i];
-  mm = mm + w1 * (gr - mm);                         // exp_avg.lerp_(grad, 1 - beta1)
-  const float vv = v[i] * beta2 + w2 * (gr * gr);   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-  const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-  pp = pp - step_size * (mm / denom);
+  float mm = m[i], vv = v[i];
+  const float pp = pfpp_adamw_element(p[i], gr, mm, vv, decay, w1, beta2, w2, eps, step_size, inv_sqrt_bc2);
   p[i] = pp; m[i] = mm; v[i] = vv;
   if (hi) {
     const pfpp_hl s = pfpp_split(pp);
@@ -607,7 +604,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
 // Adam over a list of tensors (pfpp_adam_multi): the tensors' descriptors and the launch's (tensor, chunk) block map travel in the
 // kernel-argument struct, so a step over many small tensors is a handful of launches and no device-side table exists that could be
 // stale (the engines allocate new gradient tensors every step).  Per element the arithmetic is adamw_kernel<false>'s
-// (adam_multi_element below), without planes, zero_grad and guard: the results are bit for bit pfpp_adamw's.  The pointers are only
+// (pfpp_adamw_element, adamw_element.h), without planes, zero_grad and guard: the results are bit for bit pfpp_adamw's.  The pointers are only
 // 4-byte aligned (parameters can be views), so every access is one dword; a wave's access is 256 contiguous bytes.
 constexpr int AM_TENSORS = PFPP_ADAM_MULTI_MAX_TENSORS, AM_BLOCKS = PFPP_ADAM_MULTI_MAX_BLOCKS, AM_CHUNK = PFPP_ADAM_MULTI_CHUNK;
 struct AdamMultiArgs {
@@ -624,25 +621,6 @@ struct AdamMultiArgs {
 };
 static_assert(sizeof(AdamMultiArgs) <= 4096, "the kernel-argument segment of pfpp_adam_multi is kept within 4 KB");
 static_assert(AM_TENSORS <= 256 && AM_CHUNK % (256 * 4) == 0, "blk_tensor is a byte; a chunk is whole passes of 256 threads x 4");
-
-// adamw_kernel's update of one element with its fused multiply-adds written out.  That kernel's source leaves the contraction
-// of `v * beta2 + w2 * (g * g)` (two products and a sum) and of the other three sums to the compiler, which fuses within one
-// kernel as its instruction selection happens to fall: the same source expression in this kernel came out as fma(beta2, v, w2 g^2)
-// where adamw_kernel has fma(w2, g^2, beta2 v), one rounding apart.  The forms below are adamw_kernel<false>'s as compiled for
-// gfx950, pinned: every product that is rounded on its own there is a statement of its own here, under contract(off).
-__device__ __forceinline__ float adam_multi_element(float p, float g, float& m, float& v, float decay, float w1, float beta2, float w2,
-                                                    float eps, float step_size, float inv_sqrt_bc2) {
-#pragma clang fp contract(off)
-  const float gg = g * g;
-  const float vb = v * beta2;
-  v = __builtin_fmaf(w2, gg, vb);
-  const float d = g - m;
-  m = __builtin_fmaf(w1, d, m);
-  const float denom = __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
-  const float q = m / denom;
-  const float upd = step_size * q;
-  return __builtin_fmaf(decay, p, -upd);
-}
 
 __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamMultiArgs a) {
   const int t = a.blk_tensor[blockIdx.x];
@@ -670,9 +648,44 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamMultiArgs a) 
     for (int k = 0; k < 4; ++k) {
       const int64_t i = base + (int64_t)(it * 4 + k) * 256;
       if (i >= n) continue;
-      p[i] = adam_multi_element(pp[k], gr[k], mm[k], vv[k], decay, w1, beta2, w2, eps, step_size, inv_sqrt_bc2);
+      p[i] = pfpp_adamw_element(pp[k], gr[k], mm[k], vv[k], decay, w1, beta2, w2, eps, step_size, inv_sqrt_bc2);
       m[i] = mm[k]; v[i] = vv[k];
     }
+  }
+}
+
+// pfpp_adamw_guarded over a few ranges of one flat buffer in ONE launch (pfpp_adamw_ranges): what is left of a transformer layer's
+// slice — biases, the LayerNorm affine, alignment padding — once the grouped weight-gradient launch has updated the matrices in its
+// epilogue.  The table travels in the kernel arguments; a workgroup finds its range by its first block.  Per element: adamw_kernel.
+struct AdamwRangesArgs {
+  int64_t off[PFPP_ADAMW_RANGES_MAX], len[PFPP_ADAMW_RANGES_MAX];
+  unsigned first_block[PFPP_ADAMW_RANGES_MAX];
+  int n;
+  pfpp_adamw_hp hp;
+};
+
+__global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, _Float16* __restrict__ hi, _Float16* __restrict__ lo,
+                                                           const AdamwRangesArgs a, int zero_g, int* __restrict__ overflow) {
+  int r = 0;
+  for (int k = 1; k < a.n; ++k)
+    if (blockIdx.x >= a.first_block[k]) r = k;
+  const int64_t e = (int64_t)(blockIdx.x - a.first_block[r]) * 256 + threadIdx.x;
+  if (e >= a.len[r]) return;
+  const int64_t i = a.off[r] + e;
+  const float gr = g[i] * a.hp.g_scale;
+  if (zero_g) g[i] = 0.0f;
+  if (overflow && pfpp_adamw_nonfinite(gr)) {       // the element is left untouched (adamw_kernel<true>'s rule)
+    atomicOr(overflow, 1);
+    atomicAdd(overflow + 1, 1);
+    return;
+  }
+  float mm = m[i], vv = v[i];
+  const float pp = pfpp_adamw_element(p[i], gr, mm, vv, a.hp.decay, a.hp.w1, a.hp.beta2, a.hp.w2, a.hp.eps, a.hp.step_size, a.hp.inv_sqrt_bc2);
+  p[i] = pp; m[i] = mm; v[i] = vv;
+  if (hi) {
+    const pfpp_hl s = pfpp_split(pp);
+    hi[i] = s.hi; lo[i] = s.lo;
   }
 }
 
@@ -1131,6 +1144,31 @@ extern "C" int pfpp_adamw_guarded(float* p, float* g, float* m, float* v, void* 
     hipLaunchKernelGGL(adamw_kernel<false>, grid, dim3(256), 0, st, p, g, m, v, (_Float16*)hi, (_Float16*)lo, n,
                        1.0f - lr * weight_decay, 1.0f - beta1, beta2, 1.0f - beta2, eps, lr / bc1, 1.0f / sqrtf(bc2), g_scale,
                        zero_grad ? 1 : 0, (int*)nullptr);
+  return pfpp::check_launch(__func__);
+}
+
+extern "C" int pfpp_adamw_ranges(float* p, float* g, float* m, float* v, void* hi, void* lo, const int64_t* off, const int64_t* len,
+                                 int32_t n_ranges, float lr, float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2,
+                                 float g_scale, int zero_grad, int32_t* overflow, pfpp_stream_t stream) {
+  PFPP_REQUIRE(p && g && m && v, "null pointer");
+  PFPP_REQUIRE(!hi == !lo, "hi and lo go together");
+  PFPP_REQUIRE(bc1 > 0.0f && bc2 > 0.0f, "bias corrections must be positive");
+  PFPP_REQUIRE(n_ranges >= 0 && n_ranges <= PFPP_ADAMW_RANGES_MAX, "0 .. PFPP_ADAMW_RANGES_MAX ranges");
+  PFPP_REQUIRE(n_ranges == 0 || (off && len), "null table");
+  AdamwRangesArgs a;
+  memset(&a, 0, sizeof(a));
+  unsigned blocks = 0;
+  for (int k = 0; k < n_ranges; ++k) {
+    PFPP_REQUIRE(off[k] >= 0 && len[k] >= 0 && len[k] < (1ll << 38), "range");
+    if (len[k] == 0) continue;
+    a.off[a.n] = off[k]; a.len[a.n] = len[k]; a.first_block[a.n] = blocks;
+    blocks += blocks_for(len[k], 256);
+    ++a.n;
+  }
+  if (a.n == 0) return PFPP_OK;
+  a.hp = pfpp_adamw_hp_of(lr, beta1, beta2, eps, weight_decay, bc1, bc2, g_scale);
+  hipLaunchKernelGGL(adamw_ranges_kernel, dim3(blocks), dim3(256), 0, pfpp::as_stream(stream), p, g, m, v, (_Float16*)hi, (_Float16*)lo, a,
+                     zero_grad ? 1 : 0, (int*)overflow);
   return pfpp::check_launch(__func__);
 }
 

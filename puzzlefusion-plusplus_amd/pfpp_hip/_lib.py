@@ -184,13 +184,21 @@ class TlayersArgs(C.Structure):
         ("frag_ws", _p), ("frag_ws_bytes", _i64),
         ("ada_se", _p), ("ada_dse", _p), ("ada_w", _p), ("ada_gw", _p), ("ada_gb", _p),
         ("ada_adamw_w", C.POINTER(TlayerAdamw)), ("ada_adamw_b", C.POINTER(TlayerAdamw)),
+        ("opt_fused_dw", _i32),
     ]
+
+
+class DwUpdate(C.Structure):
+    """mirror of struct pfpp_dw_update (include/pfpp.h)"""
+
+    _fields_ = ([(n, _p) for n in ("p", "m", "v", "hi", "lo")] +
+                [(n, _f32) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "bc1", "bc2", "g_scale")] + [("overflow", _p)])
 
 
 class DwJob(C.Structure):
     """mirror of struct pfpp_dw_job (include/pfpp.h)"""
 
-    _fields_ = [("dy", PlanesC), ("x", PlanesC), ("gw", _p), ("gb", _p), ("M", _i64), ("N", _i64)]
+    _fields_ = [("dy", PlanesC), ("x", PlanesC), ("gw", _p), ("gb", _p), ("M", _i64), ("N", _i64), ("upd", C.POINTER(DwUpdate))]
 
 
 class ReblockJob(C.Structure):
@@ -299,6 +307,8 @@ SIGNATURES = {
     "pfpp_sa_train_stage": [C.POINTER(SaTrainArgs), _p],
     "pfpp_sa_pad_schedule": [_p, _i64, _i64, _p, _p],
     "pfpp_adamw_guarded": [_p, _p, _p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, C.c_int, _p, _p],
+    "pfpp_adamw_ranges": [_p, _p, _p, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64), _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+                          C.c_int, _p, _p],
     "pfpp_adamw_rows": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _i64, C.c_int, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, C.c_int, _p, _p],
     # ---- plane GEMM and plane-producing forms of the training kernels
     "pfpp_gemm_planes": [C.POINTER(GemmPlanesArgs), _p],
@@ -445,6 +455,7 @@ STRUCT_MIRRORS = {
     "sa_train_args": SaTrainArgs, "gemm_grad_args": GemmGradArgs, "tlayer_params": TlayerParams, "tlayer_grads": TlayerGrads,
     "tlayer_adamw": TlayerAdamw, "tlayers_args": TlayersArgs, "pw": PwC, "elayer_params": ElayerParams,
     "tlayers_eval_args": TlayersEvalArgs, "head_params": HeadParams, "head_grads": HeadGrads, "reblock_job": ReblockJob, "dw_job": DwJob,
+    "dw_update": DwUpdate,
 }
 
 ACT = {"none": 0, "relu": 1, "silu": 2, "gelu": 3, "geglu": 4}

@@ -99,7 +99,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     hipcc = _hipcc()
     objdir = CSRC / "build"
     objdir.mkdir(exist_ok=True)
-    headers = [INCLUDE / "pfpp.h", CSRC / "pfpp_common.h", CSRC / "attn_choice.h", CSRC / "gemm_common.h", CSRC / "lds_asm.h", CSRC / "sa_common.h",
+    headers = [INCLUDE / "pfpp.h", CSRC / "pfpp_common.h", CSRC / "adamw_element.h", CSRC / "attn_choice.h", CSRC / "gemm_common.h", CSRC / "lds_asm.h", CSRC / "sa_common.h",
                CSRC / "sinkhorn_common.h", CSRC / "attn_rows16.h", CSRC / "ptf_common.h", CSRC / "horn_common.h", CSRC / "mesh_common.h"]
     # the linked library newer than every source and header: nothing to do — also where the object files did not travel (the GPU box
     # gets libpfpp_hip.so but not csrc/build/, .gpurunignore): without this a test fixture there would recompile all 25 units

@@ -109,6 +109,11 @@ class FlatParams:
         self._embed_buf = None
         self.embed_fused = False           # set by the engine: the forward takes the one-launch token embedding
         self._clean = False
+        # every element of `grads` is zero (in stream order) and nothing has accumulated into it since: true from construction, after
+        # zero_grad() and after optimizer_step(zero_grad=True); a backward clears it.  What lets an armed backward update the block
+        # matrices in the weight-gradient launch's epilogue (arm_optimizer(fused_update=...)): a gradient accumulated onto zero is the
+        # value itself, and the ranges it never writes are still zero afterwards, as optimizer_step(zero_grad=True) promises
+        self._zero = True
         with torch.no_grad():
             for n in self.order:
                 p = named[n]
@@ -172,6 +177,7 @@ class FlatParams:
         if not self._clean:                # optimizer_step(zero_grad=True) already cleared the buffer in its own pass
             self.grads.zero_()
         self._clean = False                # whoever asks for zeros is about to accumulate into them
+        self._zero = True
 
     # -- kernel-side operands ------------------------------------------------------------------------
     def operands(self) -> Dict[str, object]:
@@ -349,6 +355,8 @@ class DenoiserTrainEngine:
         self._overflow = torch.zeros(2, dtype=torch.int32, device=self.flat.params.device) if self._guard else None
         self._ovf_ring = None
         self._backoff = 1.0                          # power of two <= 1 applied on top of the dpred-tracking scale
+        self._armed_fused = None
+        self._zero_on_entry = False
         self._clean_steps = 0
         self.overflow_steps = 0                      # optimizer steps in which non-finite gradients were seen (and skipped)
         # weight / bias gradients are off the critical path (only the optimizer needs them): they run on a second
@@ -828,8 +836,12 @@ class DenoiserTrainEngine:
             args.bc1, args.bc2 = 1.0 - hp["betas"][0] ** step, 1.0 - hp["betas"][1] ** step
             args.opt_g_scale, args.opt_zero_grad = 1.0, int(self._armed_zero)
             args.overflow = self._overflow.data_ptr() if self._overflow is not None else None
+            # the block matrices' AdamW in the grouped weight-gradient launch's epilogue: the library takes it where its own conditions
+            # hold (armed, zero_grad, side stream, grouped launch); this side vouches for the zeroed gradient buffer
+            args.opt_fused_dw = int(self._armed_fused is not False and self._armed_zero and self._zero_on_entry)
         else:
             args.adamw = None
+            args.opt_fused_dw = 0
         side_arg = C_.c_void_p(side_h) if side_h is not None else None
         if not reducing:
             _lib.check(lib.pfpp_tlayers_bwd(C_.byref(args), 0, self.num_layers, C_.c_void_p(main_h), side_arg), "pfpp_tlayers_bwd")
@@ -915,6 +927,7 @@ class DenoiserTrainEngine:
             self._accumulated = True             # this step's table gradients are no longer "the rows of one batch": exchange them densely
         self.flat.attach_grads()
         self.flat._clean = False                 # gradients are about to be accumulated
+        self._zero_on_entry, self.flat._zero = self.flat._zero, False
         ops_ = self.flat.operands()
         w, g = ops_["w"], ops_["g"]
         s = ctx.t
@@ -1364,14 +1377,21 @@ class DenoiserTrainEngine:
 
     # ------------------------------------------------------------------------------------------ optimizer
     def arm_optimizer(self, *, lr: float = 2e-4, betas=(0.95, 0.999), eps: float = 1e-8, weight_decay: float = 1e-6,
-                      zero_grad: bool = False) -> None:
+                      zero_grad: bool = False, fused_update: Optional[bool] = None) -> None:
         """optimizer-in-backward for the NEXT backward: every transformer layer's parameters take their AdamW update as soon as
         the layer's gradients are final (on the weight-gradient stream, under the rest of the backward); optimizer_step() with
         the same hyper-parameters then updates only what is left (embeddings, AdaLN tables and linears, output heads) and
         closes the step.  Same arithmetic per element as one launch over the flat buffer.  With N > 1 ranks the layer's update is
         queued behind the layer's all-reduce on the exchange stream (1 / world folded in), so the multi-rank step keeps the
         schedule the single-rank line is measured on.  One-shot; ignored (everything happens in optimizer_step) without a second
-        stream at N = 1, and for backward passes under no_sync() (gradient accumulation: nothing is final yet)."""
+        stream at N = 1, and for backward passes under no_sync() (gradient accumulation: nothing is final yet).
+        fused_update: None / True = where it is valid, the six matrices of a block take their update in the epilogue of the block's
+        grouped weight-gradient launch and their gradients never pass through memory (single rank, zero_grad=True, a second stream, the
+        C sequencer's grouped launch, and a gradient buffer that is all zero when the backward starts: after flat.zero_grad() or a
+        step with zero_grad=True, with no backward in between); everywhere else, and with False, the layer's AdamW launch reads them
+        back.  Bit for bit the same parameters, moments, planes and overflow flag either way; flat.grads is all zero after the step
+        either way (the fused form never wrote the matrices' ranges)."""
+        self._armed_fused = fused_update
         self._armed = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay))
         self._armed_zero = bool(zero_grad)          # the per-layer updates also clear their gradients (optimizer_step(zero_grad=True))
         self._early = []
@@ -1435,11 +1455,11 @@ class DenoiserTrainEngine:
                 if a > pos:
                     self._adamw_range(pos, a, step=self.step_count, g_scale=g_scale, zero_grad=zero_grad, **hp)
                 pos = max(pos, b)
-            f._clean = bool(zero_grad)
+            f._clean = f._zero = bool(zero_grad)
         else:
             pos = self._adamw_tables_active(0, f.params.numel(), True, g_scale, zero_grad, hp)
             self._adamw_range(pos, f.params.numel(), step=self.step_count, g_scale=g_scale, zero_grad=zero_grad, **hp)
-            f._clean = bool(zero_grad)
+            f._clean = f._zero = bool(zero_grad)
         self._join_side()                 # (deferred by _all_done: the launches above ran under the weight-gradient stream's tail)
         self._after_step_overflow()
         f.after_optimizer_step()
